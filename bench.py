@@ -28,10 +28,15 @@ parent never touches the GPU) and fails when fewer than N GPUs are visible.
 
 Prints ONE JSON line (rank 0).  `roofline` is step level: the workload's
 algorithmic bytes (DESIGN.md 4 for the backward terms) over
-ms_per_step against the 8 TB/s HBM peak; its `kernel` entry prices the
-dominant kernel from its in-step duration, HIP events on the stream it runs
-on.  `cpu_baseline` times the CPU restatement (oracle/, the "port") on a
-bounded sample of the same workload on this box's host cores.
+ms_per_step against the 8 TB/s HBM peak.
+
+A plain run does what that line's `value` / `ms_per_step` need: set-up, the
+settle calls, the warm-up and the timed steps.  `--full` adds the rest: the
+output check before the warm-up (`outputs_verified`), `roofline.kernel`,
+which prices the dominant kernel from its in-step duration (HIP events on
+the stream it runs on), and `cpu_baseline`, which times the CPU restatement
+(oracle/, the "port") on a bounded sample of the same workload on the host
+cores.  `--dump-outputs DIR` writes the last timed step's outputs as .npy.
 """
 import argparse
 import json
@@ -54,6 +59,7 @@ import torch.distributed as dist  # noqa: E402
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md chip table)
 VALU_PEAK_TFLOPS = 157.3   # MI355X fp32 vector peak (packed FMA), SURVEY.md 8d
 METRIC = "point-clouds/sec (1024 pts, k=32) PPF+sph-vox forward"
+DUMP_BYTES = 60 * 1000 * 1000  # --dump-outputs writes at most this much array data
 
 DEFAULTS = {  # workload: (clouds per GPU, points, k, r, channels)
     "extract": (32, 1024, 32, 32, 64),
@@ -119,7 +125,22 @@ def parse(argv=None):
                     help="distinct input batches cycled through the timed steps (extract / "
                          "pairs: the runner's batch ring, each batch with its own output set; "
                          "default 20 extract, 8 pairs, 4 c3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the output check "
+                         "before the warm-up, the timing events around the dominant kernel "
+                         "(roofline.kernel, roofline.traffic) and the CPU baseline after the "
+                         "timed steps (each can still be switched off with its --no-* flag); "
+                         "without --full a run sets up, settles, warms up, times the steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step "
+                         "(the arrays a caller of the timed path receives) as DIR/<name>.npy, "
+                         "float32 (float64 where an integer output does not fit float32); an "
+                         "output of more than DUMP_BYTES / 8 / (number of outputs) elements is "
+                         "written as a fixed, seeded sample of that many of its elements")
     args = ap.parse_args(argv)
+    if not args.full:
+        args.no_verify = args.no_kernel_timing = args.no_cpu_baseline = True
     b, n, k, r, c = DEFAULTS[args.workload]
     args.batch = b if args.batch is None else args.batch
     args.points = n if args.points is None else args.points
@@ -433,6 +454,13 @@ class ExtractWorkload:
         torch.cuda.current_stream(self.dev).wait_stream(self.origin)
         return out
 
+    def last_outputs(self):
+        """The ring set the last step wrote (run() leaves next_set one past it)."""
+        pairs = self.args.workload == "pairs"
+        sx = self.ex.ex if pairs else self.ex
+        ring = sx.ring_outputs(self.R, self.ex.pairs if pairs else 0)
+        return dict(ring[(self.next_set - 1) % self.R])
+
     def kernel_report(self):
         ms = self.ex.grid_kernel_times()
         avg = sum(ms) / len(ms) if ms else float("nan")
@@ -516,6 +544,9 @@ class C3Workload:
         vox_bwd = 8 * n + 8 * c * n
         self.step_bytes = fwd * b + self.devox_bwd_bytes + vox_bwd * b
         self.t = []
+        # the timed call keeps its last step's outputs (references only) for
+        # last_outputs(); other calls keep none, so they free theirs as before
+        self.keep_last, self.last = False, None
 
     def _backward(self, s, out, ev=None):
         """Step s's backward share: devox backward of its synthetic upstream
@@ -536,12 +567,16 @@ class C3Workload:
             res = self._backward(s, out, self.ev[s - first] if timed else None)
             if keep is not None:
                 keep.append((out, res))
+            if self.keep_last and s == first + steps - 1:
+                self.last = (out, res)
 
     def _pipelined(self, steps, timed, keep=None):
         def consume(s, out):
             res = self._backward(s, out, self.ev[s] if timed else None)
             if keep is not None:
                 keep.append(({kk: v.clone() for kk, v in out.items()}, res))
+            if self.keep_last and s == steps - 1:
+                self.last = (out, res)
         # prefetch: batch(s + 1) before step s's voxel side and consume; the
         # bench's batch tensors are read-only, so that is allowed.  The voxel
         # head (prep + means + devox) of batch s + 1 runs ahead on a side
@@ -590,6 +625,7 @@ class C3Workload:
         # voxel stage -- means + devox, then the dense-grid stream -- on the
         # caller's stream, KNN + PPF one batch ahead on s_nbr)
         t = timed and not self.args.no_kernel_timing
+        self.keep_last = timed
         if self.main_stream is not None:
             self.main_stream.wait_stream(torch.cuda.current_stream(self.dev))
             with torch.cuda.stream(self.main_stream):
@@ -602,8 +638,14 @@ class C3Workload:
             self._serial(steps, t)
         else:
             self._pipelined(steps, t)
+        self.keep_last = False
         self.timed_steps = steps if timed else 0
         return steps
+
+    def last_outputs(self):
+        """The last timed step's forward outputs and its two backward results."""
+        out, (gg, gx) = self.last
+        return dict(out, grad_grid=gg, grad_x=gx)
 
     def kernel_report(self):
         """The step's dominant kernel by in-step duration (HIP events on the
@@ -798,16 +840,26 @@ class C5Workload:
             self.side.wait_stream(cur)
             with torch.cuda.stream(self.side):
                 nc = ops.spherical_normalize(xyz)
-                grid, ind, _ = ops.spherical_avg_voxelize_forward(feat, nc, a.res)
-                ops.spherical_trilinear_devoxelize_forward(a.res, True, nc, grid, ind)
+                grid, ind, cnt = ops.spherical_avg_voxelize_forward(feat, nc, a.res)
+                dv = ops.spherical_trilinear_devoxelize_forward(a.res, True, nc, grid, ind)
             if timed and not a.no_kernel_timing:
                 self.ev[s][0].record()
-            ops.knn_local_ppf(xyz, nrm, a.k)
+            nb = ops.knn_local_ppf(xyz, nrm, a.k)
             if timed and not a.no_kernel_timing:
                 self.ev[s][1].record()
             cur.wait_stream(self.side)
+            if timed and s == steps - 1:
+                # references only, for last_outputs(); made on the side
+                # stream, read after the synchronize that ends the timed region
+                self.last = {"norm_coords": nc, "grid": grid, "ind": ind, "cnt": cnt,
+                             "devox": dv[0], "dinds": dv[1], "dwgts": dv[2],
+                             "knn_idx": nb[0], "local_ppf": nb[1]}
+            del dv, nb  # every other step frees them here, as before
         self.timed_steps = steps if timed else 0
         return steps
+
+    def last_outputs(self):
+        return self.last
 
     def kernel_report(self):
         ms = [x.elapsed_time(y) for x, y in self.ev[:self.timed_steps]] \
@@ -853,6 +905,13 @@ def settle_runs(wl, args, dev):
         else args.steps
     m = max(1, m)
     t0 = time.perf_counter()
+    if args.no_verify:
+        # no output check ran, so the process's first call pays the one-off
+        # costs (code objects loaded, buffers made: ~13 ms against ~1.5 ms
+        # for a 20-step c2 call); the call that sizes `calls` comes after it
+        wl.run(m, timed=False)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
     wl.run(m, timed=False)
     torch.cuda.synchronize(dev)
     # the same number of calls on every rank (the calls all-gather)
@@ -866,6 +925,27 @@ def settle_runs(wl, args, dev):
         torch.cuda.synchronize(dev)
     return {"ms": round((time.perf_counter() - t0) * 1e3, 1), "calls": calls,
             "steps_per_call": m}
+
+
+def dump_outputs(outputs, path):
+    """Write {name: tensor} as path/<name>.npy, float32 (float64 for an
+    integer tensor whose values do not all fit float32's 24 bits).  At most
+    DUMP_BYTES in all: a tensor of more than cap = DUMP_BYTES / 8 / len(outputs)
+    elements is written as its elements at cap flat positions drawn once
+    from a fixed seed (the same positions for the same shape in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // 8 // max(1, len(outputs))
+    for name in sorted(outputs):
+        t = outputs[name].detach()
+        if t.numel() > cap:
+            pos = np.sort(np.random.default_rng(20240).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        if t.is_floating_point() or t.numel() == 0 or int(t.abs().max()) < 1 << 24:
+            t = t.to(torch.float32)
+        else:
+            t = t.to(torch.float64)
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def main(argv=None):
@@ -913,7 +993,9 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    step_traffic, kernel = wl.kernel_report()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(wl.last_outputs(), args.dump_outputs)
+    step_traffic, kernel = wl.kernel_report() if args.full else (None, None)
     value = args.batch * world * args.steps / elapsed
     # per rank: every rank moves its own HBM
     step_gbs = wl.step_bytes * args.steps / elapsed / 1e9

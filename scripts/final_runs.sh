@@ -14,11 +14,11 @@ run() {  # name limit cmd...
 }
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 run pytest_gpu 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider
-run bench_c2 200 python bench.py
-run bench_c2_driver 200 python bench.py --steps 20 --warmup 5
-run bench_pairs 300 python bench.py --workload pairs
-run bench_c3 300 python bench.py --workload c3
-run bench_c5 300 python bench.py --workload c5
+run bench_c2 200 python bench.py --full
+run bench_c2_driver 200 python bench.py --full --steps 20 --warmup 5
+run bench_pairs 300 python bench.py --full --workload pairs
+run bench_c3 300 python bench.py --full --workload c3
+run bench_c5 300 python bench.py --full --workload c5
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 run prof_c2 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c2 -o run --output-format csv -- python3 bench.py --steps 80 --warmup 40 --no-cpu-baseline --no-verify
 run prof_c3 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c3 -o run --output-format csv -- python3 bench.py --workload c3 --steps 10 --no-cpu-baseline

@@ -13,8 +13,8 @@ run() {  # name limit cmd...
 }
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 run pytest_gpu 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider
-run bench_c2 200 python bench.py
-run bench_c2_driver 200 python bench.py --steps 20 --warmup 5
-run bench_pairs 300 python bench.py --workload pairs
-run bench_c3 300 python bench.py --workload c3
-run bench_c5 300 python bench.py --workload c5
+run bench_c2 200 python bench.py --full
+run bench_c2_driver 200 python bench.py --full --steps 20 --warmup 5
+run bench_pairs 300 python bench.py --full --workload pairs
+run bench_c3 300 python bench.py --full --workload c3
+run bench_c5 300 python bench.py --full --workload c5

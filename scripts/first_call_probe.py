@@ -18,7 +18,7 @@ TRIALS = int(os.environ.get("TRIALS", "6"))
 PRE = int(os.environ.get("PRE", "0"))
 PRE_CALL = int(os.environ.get("PRE_CALL", "0"))  # steps per pre call (0: bench's chunking)
 PRE_SLEEP = float(os.environ.get("PRE_SLEEP", "0"))  # host sleep (s) after the pre phase
-args = bench.parse(sys.argv[1:] or ["--steps", "20", "--warmup", "5"])
+args = bench.parse(["--full"] + (sys.argv[1:] or ["--steps", "20", "--warmup", "5"]))
 torch.cuda.set_device(0)
 dev = torch.device("cuda", 0)
 t_start = time.perf_counter()
