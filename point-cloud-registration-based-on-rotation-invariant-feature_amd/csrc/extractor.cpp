@@ -111,16 +111,10 @@ pcr_status knn_select_ppf(const pcr_extractor_args* a, const StepIO& io, int q, 
   if (!sorted)  // no sorted path: the one-call selection + PPF
     return pcr_knn_local_ppf(io.xyz, io.normals, a->b, a->n, a->k, a->relative, io.knn_idx,
                              io.knn_dist, io.local_ppf, a->knn_ws[q], a->knn_ws_bytes, st);
-  if (io.knn_dist) {  // distances requested: the selection writes in original order
-    PCR_TRY(pcr_knn_local_ppf_prepared(io.xyz, io.normals, a->b, a->n, a->k, a->relative,
-                                         io.knn_idx, io.knn_dist, nullptr, a->knn_ws[q],
-                                         a->knn_ws_bytes, st));
-    return pcr_local_ppf_forward(io.xyz, io.normals, io.xyz, io.normals, io.knn_idx, a->b, a->n,
-                                 a->n, a->k, 1, a->relative, io.local_ppf, st);
-  }
-  // selection in sorted query order, the PPF launch writes knn_idx + PPF
-  return pcr_knn_select_ppf(io.xyz, io.normals, a->b, a->n, a->k, a->relative, io.knn_idx,
-                            io.local_ppf, a->knn_ws[q], a->knn_ws_bytes, st);
+  // sorted-rows selection + PPF, or (distances requested, or no such path)
+  // selection in original order + the PPF launch
+  return knn_select_ppf_prepared(io.xyz, io.normals, a->b, a->n, a->k, a->relative, io.knn_idx,
+                                 io.knn_dist, io.local_ppf, a->knn_ws[q], a->knn_ws_bytes, st);
 }
 
 // the step's registration matching (source clouds [0, P) against targets

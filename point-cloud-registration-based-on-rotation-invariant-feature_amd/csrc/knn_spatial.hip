@@ -1612,6 +1612,8 @@ __global__ __launch_bounds__(NW * 64) void knn_select_kernel(
 // 12 waves cost pairs 9% (312-315k against 341-343k clouds/s).
 template <int W>
 constexpr int wsel_chunk() { return W == 8 ? 2 : 1; }
+// true: W = 8 (more than 4096 waves at W = 8), false: W = 12
+static inline bool wsel_narrow(int nblk, int b) { return (size_t)nblk * b * 8 > 4096; }
 constexpr int kWselCap = 64;   // keys collected per query (one per lane)
 constexpr int kWselTmax = 0x461C3FFF;  // bits of the largest float below 10000
 
@@ -2082,32 +2084,47 @@ __global__ __launch_bounds__(256) void knn_pack_rec_kernel(const float* __restri
   r[1] = float4{N[i + m], N[i + 2 * (size_t)m], 0.0f, 0.0f};
 }
 
+// One direction of a selection (queries qs against candidates cs): its
+// outputs and, for the fused local PPF, both sets' original coordinates and
+// normals.  Anything may be null.
+struct KnnDir {
+  float* dist = nullptr;
+  int* idx = nullptr;
+  const float *qxyz = nullptr, *qnrm = nullptr, *cxyz = nullptr, *cnrm = nullptr;
+  int relative = 0;
+  float* ppf = nullptr;
+};
+
+// What knn_select_kernel writes (its sorted_emit argument)
+enum KnnEmit : int {
+  kEmitOriginal = 0,    // dist / idx (+ PPF) in original query order
+  kEmitSortedRows = 1,  // neighbour ids in sorted query order (qs.sidx rows)
+  kEmitSortedKeys = 2,  // keys in sorted query order (qs.skey), then knn_emit_kernel
+};
+
 template <bool PPF>
-static void launch_emit(const KnnSet& qs, const KnnSet& cs, int b, int k, float* dist, int* idx,
-                        const float* qxyz, const float* qnrm, const float* cxyz,
-                        const float* cnrm, int relative, float* ppf, hipStream_t st) {
+static void launch_emit(const KnnSet& qs, const KnnSet& cs, int b, int k, const KnnDir& d,
+                        hipStream_t st) {
   const int nqb = ceil_div(qs.n, kBlk);
   // the candidates' records, in the candidate set's workspace
   if (PPF)
-    hipLaunchKernelGGL(knn_pack_rec_kernel, dim3(ceil_div(cs.n, 256), b), dim3(256), 0, st, cxyz,
-                       cnrm, cs.n, cs.rec);
-  hipLaunchKernelGGL((knn_emit_kernel<PPF>), dim3(nqb * b), dim3(256), 0, st, qs, k, nqb, dist,
-                     idx, qxyz, qnrm, cs.rec, cs.n, relative, ppf);
+    hipLaunchKernelGGL(knn_pack_rec_kernel, dim3(ceil_div(cs.n, 256), b), dim3(256), 0, st,
+                       d.cxyz, d.cnrm, cs.n, cs.rec);
+  hipLaunchKernelGGL((knn_emit_kernel<PPF>), dim3(nqb * b), dim3(256), 0, st, qs, k, nqb, d.dist,
+                     d.idx, d.qxyz, d.qnrm, cs.rec, cs.n, d.relative, d.ppf);
 }
 
 template <int NW, bool PPF, int CAP = kCap, int KSEL = kSelMaxK>
-static void launch_select(const KnnSet& qs, const KnnSet& cs, int b, int k, float* dist,
-                          int* idx, const float* qxyz, const float* qnrm, const float* cxyz,
-                          const float* cnrm, int relative, float* ppf, hipStream_t st,
-                          int sorted_emit = 0) {
+static void launch_select(const KnnSet& qs, const KnnSet& cs, int b, int k, const KnnDir& d,
+                          hipStream_t st, KnnEmit emit = kEmitOriginal) {
   // a wave sees ceil(nblk / NW) * 64 candidates: byte fields when that fits
   PCR_PRIO_INIT();
   const int per_wave = ceil_div(cs.nblk, NW) * kBlk;
   const dim3 grid(qs.nblk, b), blk(NW * 64);
 #define PCR_SEL(CBV, CLV, CACHEV)                                                             \
   hipLaunchKernelGGL((knn_select_kernel<NW, CBV, CLV, PPF, CAP, KSEL, CACHEV>), grid, blk, 0, st, \
-                     qs, cs, k, dist, idx, qxyz, qnrm, cxyz, cnrm, relative, ppf,              \
-                     sorted_emit)
+                     qs, cs, k, d.dist, d.idx, d.qxyz, d.qnrm, d.cxyz, d.cnrm, d.relative,     \
+                     d.ppf, (int)emit)
   if constexpr (CAP == kCap) {
     // c3 clouds (2048 points): 32 KB of candidates in LDS, two workgroups per CU
     if (cs.npad > kSelCache && cs.npad <= 2 * kSelCache) {
@@ -2123,6 +2140,7 @@ static void launch_select(const KnnSet& qs, const KnnSet& cs, int b, int k, floa
     PCR_SEL(16, false, kSelCache);
 #undef PCR_SEL
 }
+
 
 size_t knn_ws_size(int b, int n, int m) {
   size_t off = knn_set_layout(b, n, nullptr, nullptr, 0);
@@ -2163,107 +2181,89 @@ static void launch_sort(const float* pts, int b, int n, const KnnSet& s, hipStre
   }
 }
 
-template <int KM, bool PPF>
-static void launch_block_k(const KnnSet& qs, const KnnSet& cs, int b, int k, float* dist,
-                           int* idx, const float* qxyz, const float* qnrm, const float* cxyz,
-                           const float* cnrm, int relative, float* ppf, hipStream_t st) {
-  dim3 grid(ceil_div(qs.nblk, KnnNW<KM>::wg / KnnNW<KM>::value), b);
-  hipLaunchKernelGGL((knn_block_kernel<KM, PPF>), grid, dim3(KnnNW<KM>::wg * 64), 0, st, qs, cs, k,
-                     dist, idx,
-                     qxyz, qnrm, cxyz, cnrm, relative, ppf);
-}
-
 template <bool PPF>
-static pcr_status launch_block(const KnnSet& qs, const KnnSet& cs, int b, int k, float* dist,
-                               int* idx, const float* qxyz, const float* qnrm, const float* cxyz,
-                               const float* cnrm, int relative, float* ppf, hipStream_t st,
-                               int sorted_emit = 0) {
+static pcr_status launch_block(const KnnSet& qs, const KnnSet& cs, int b, int k, const KnnDir& d,
+                               hipStream_t st, KnnEmit emit = kEmitOriginal) {
   const bool sel = k <= kSelMaxK || (k <= kSelMaxK64 && cs.npad > kSelCache);
-  if (sel && sorted_emit == 0 && qs.skey != nullptr) {
+  if (sel && emit == kEmitOriginal && qs.skey != nullptr) {
     // queries past kSortedMaxN: keys in sorted query order, then un-permuted
     if (k <= kSelMaxK)
-      launch_select<8, false>(qs, cs, b, k, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              0, nullptr, st, 2);
+      launch_select<8, false>(qs, cs, b, k, KnnDir{}, st, kEmitSortedKeys);
     else
-      launch_select<8, false, kCap64, kSelMaxK64>(qs, cs, b, k, nullptr, nullptr, nullptr,
-                                                  nullptr, nullptr, nullptr, 0, nullptr, st, 2);
-    launch_emit<PPF>(qs, cs, b, k, dist, idx, qxyz, qnrm, cxyz, cnrm, relative, ppf, st);
+      launch_select<8, false, kCap64, kSelMaxK64>(qs, cs, b, k, KnnDir{}, st, kEmitSortedKeys);
+    launch_emit<PPF>(qs, cs, b, k, d, st);
     return PCR_OK;
   }
   if (k <= kSelMaxK) {
-    launch_select<8, PPF>(qs, cs, b, k, dist, idx, qxyz, qnrm, cxyz, cnrm, relative, ppf, st,
-                          sorted_emit);
+    launch_select<8, PPF>(qs, cs, b, k, d, st, emit);
   } else if (k <= kSelMaxK64 && cs.npad > kSelCache) {
     // large clouds (BASELINE c5, k = 64): the pruned threshold selection with
     // room for 2.75 k collected keys per query
-    launch_select<8, PPF, kCap64, kSelMaxK64>(qs, cs, b, k, dist, idx, qxyz, qnrm, cxyz, cnrm,
-                                              relative, ppf, st);
-  } else if (k <= 16)
-    launch_block_k<16, PPF>(qs, cs, b, k, dist, idx, qxyz, qnrm, cxyz, cnrm, relative, ppf, st);
-  else if (k <= 32)
-    launch_block_k<32, PPF>(qs, cs, b, k, dist, idx, qxyz, qnrm, cxyz, cnrm, relative, ppf, st);
-  else if (k <= 64)
-    launch_block_k<64, PPF>(qs, cs, b, k, dist, idx, qxyz, qnrm, cxyz, cnrm, relative, ppf, st);
-  else if (k <= 128)
-    launch_block_k<128, PPF>(qs, cs, b, k, dist, idx, qxyz, qnrm, cxyz, cnrm, relative, ppf, st);
-  else
-    return PCR_ERR_UNSUPPORTED;
+    launch_select<8, PPF, kCap64, kSelMaxK64>(qs, cs, b, k, d, st);
+  } else {
+    const bool ok = with_kmax(k, [&](auto km) {
+      constexpr int KM = decltype(km)::value;
+      const dim3 grid(ceil_div(qs.nblk, KnnNW<KM>::wg / KnnNW<KM>::value), b);
+      hipLaunchKernelGGL((knn_block_kernel<KM, PPF>), grid, dim3(KnnNW<KM>::wg * 64), 0, st, qs,
+                         cs, k, d.dist, d.idx, d.qxyz, d.qnrm, d.cxyz, d.cnrm, d.relative, d.ppf);
+    });
+    if (!ok) return PCR_ERR_UNSUPPORTED;
+  }
   return PCR_OK;
 }
 
 // Returns PCR_ERR_UNSUPPORTED (nothing launched) when the spatial path does
 // not apply; the caller then uses the brute-force kernels.
 pcr_status knn_spatial(const float* xyz1, const float* xyz2, int b, int n, int m, int k,
-                       float* dist1, int* idx1, float* dist2, int* idx2, const float* nrm1,
-                       const float* nrm2, int relative, float* ppf1, void* ws, size_t ws_bytes,
-                       bool self, hipStream_t st, int stages) {
+                       const KnnIO& io, void* ws, size_t ws_bytes, bool self, hipStream_t st,
+                       int stages) {
   if (ws == nullptr || n > kKnnMaxN || m > kKnnMaxN || n < 1 || m < 1 || k > 128)
     return PCR_ERR_UNSUPPORTED;
   if (ws_bytes < knn_ws_size(b, n, m)) return PCR_ERR_UNSUPPORTED;
   KnnSet s1, s2;
   size_t off = knn_set_layout(b, n, &s1, (char*)ws, 0);
   knn_set_layout(b, m, &s2, (char*)ws, off);
-  if (stages & 1) {
+  if (stages & kKnnSort) {
     launch_sort(xyz1, b, n, s1, st);
     if (!self) launch_sort(xyz2, b, m, s2, st);
   }
-  if (!(stages & 2)) return PCR_OK;
+  if (!(stages & kKnnSelect)) return PCR_OK;
   const KnnSet& c1 = self ? s1 : s2;
-  pcr_status rc;
-  if (stages & 4) {
+  if (stages & kKnnSortedRows) {
     // selection only, neighbour ids in sorted query order into s1.sidx (the
     // cached selection, k <= kSortedK); the caller's PPF launch un-permutes
-    if (!self || ppf1 || dist1 || idx2 || k > kSortedK || k > kSelMaxK || s1.sidx == nullptr ||
-        s1.npad > 2 * kSelCache)
+    if (!self || io.ppf1 || io.dist1 || io.idx2 || k > kSortedK || k > kSelMaxK ||
+        s1.sidx == nullptr || s1.npad > 2 * kSelCache)
       return PCR_ERR_UNSUPPORTED;
     // clouds of <= 1024 points: the transposed selection (c2: 31.0 us alone
     // against 32.8 for knn_select_kernel).  At 2048 points its R = 32
     // registers per coordinate leave 2 waves per SIMD and it lost (928 us
     // against 600 at c3), so those keep the per-lane kernel.
     if (s1.npad <= 16 * kBlk) {
-      if ((size_t)s1.nblk * b * 8 <= 4096)
-        hipLaunchKernelGGL((knn_wsel_kernel<16, 12>), dim3(s1.nblk, b), dim3(12 * 64), 0, st, s1,
+      if (wsel_narrow(s1.nblk, b))
+        hipLaunchKernelGGL((knn_wsel_kernel<16, 8>), dim3(s1.nblk, b), dim3(8 * 64), 0, st, s1,
                            k);
       else
-        hipLaunchKernelGGL((knn_wsel_kernel<16, 8>), dim3(s1.nblk, b), dim3(8 * 64), 0, st, s1,
+        hipLaunchKernelGGL((knn_wsel_kernel<16, 12>), dim3(s1.nblk, b), dim3(12 * 64), 0, st, s1,
                            k);
       return PCR_OK;
     }
-    return launch_block<false>(s1, c1, b, k, nullptr, idx1, nullptr, nullptr, nullptr, nullptr,
-                               0, nullptr, st, 1);
+    return launch_block<false>(s1, c1, b, k, KnnDir{nullptr, io.idx1}, st, kEmitSortedRows);
   }
-  if (ppf1)
-    rc = launch_block<true>(s1, c1, b, k, dist1, idx1, xyz1, nrm1, xyz2, nrm2, relative, ppf1, st);
+  pcr_status rc;
+  if (io.ppf1)
+    rc = launch_block<true>(s1, c1, b, k,
+                            KnnDir{io.dist1, io.idx1, xyz1, io.nrm1, xyz2, io.nrm2, io.relative,
+                                   io.ppf1},
+                            st);
   else
-    rc = launch_block<false>(s1, c1, b, k, dist1, idx1, nullptr, nullptr, nullptr, nullptr, 0,
-                             nullptr, st);
+    rc = launch_block<false>(s1, c1, b, k, KnnDir{io.dist1, io.idx1}, st);
   if (rc != PCR_OK) return rc;
-  if (idx2) rc = launch_block<false>(c1, s1, b, k, dist2, idx2, nullptr, nullptr, nullptr, nullptr,
-                                     0, nullptr, st);
+  if (io.idx2) rc = launch_block<false>(c1, s1, b, k, KnnDir{io.dist2, io.idx2}, st);
   return rc;
 }
 
-// the sorted-order outputs of a self KNN workspace (knn_spatial stage 4)
+// the sorted-order outputs of a self KNN workspace (kKnnSortedRows)
 bool knn_sorted_views(void* ws, int b, int n, const int** sidx, const int** inv, int* npad) {
   KnnSet s;
   knn_set_layout(b, n, &s, (char*)ws, 0);

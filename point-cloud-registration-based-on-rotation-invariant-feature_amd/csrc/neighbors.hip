@@ -1024,22 +1024,12 @@ template <bool PPF, int CC>
 static pcr_status launch_knn_c(const float* xyz1, const float* xyz2, int b, int c, int n, int m,
                                int k, float* dist, int* idx, const float* normals, int relative,
                                float* ppf, hipStream_t st) {
-  dim3 grid(ceil_div(n, kKnnThreads), b);
-  if (k <= 16)
-    hipLaunchKernelGGL((knn_kernel<16, PPF, CC>), grid, dim3(kKnnThreads), 0, st, xyz1, xyz2, c,
-                       n, m, k, dist, idx, normals, relative, ppf);
-  else if (k <= 32)
-    hipLaunchKernelGGL((knn_kernel<32, PPF, CC>), grid, dim3(kKnnThreads), 0, st, xyz1, xyz2, c,
-                       n, m, k, dist, idx, normals, relative, ppf);
-  else if (k <= 64)
-    hipLaunchKernelGGL((knn_kernel<64, PPF, CC>), grid, dim3(kKnnThreads), 0, st, xyz1, xyz2, c,
-                       n, m, k, dist, idx, normals, relative, ppf);
-  else if (k <= 128)
-    hipLaunchKernelGGL((knn_kernel<128, PPF, CC>), grid, dim3(kKnnThreads), 0, st, xyz1, xyz2, c,
-                       n, m, k, dist, idx, normals, relative, ppf);
-  else
-    return PCR_ERR_UNSUPPORTED;
-  return PCR_OK;
+  const dim3 grid(ceil_div(n, kKnnThreads), b);
+  const bool ok = with_kmax(k, [&](auto km) {
+    hipLaunchKernelGGL((knn_kernel<decltype(km)::value, PPF, CC>), grid, dim3(kKnnThreads), 0, st,
+                       xyz1, xyz2, c, n, m, k, dist, idx, normals, relative, ppf);
+  });
+  return ok ? PCR_OK : PCR_ERR_UNSUPPORTED;
 }
 
 template <bool PPF>
@@ -1065,9 +1055,11 @@ extern "C" pcr_status pcr_knn_forward(const float* xyz1, const float* xyz2, int 
   PCR_REQUIRE(dist1 && dist2 && idx1 && idx2, "knn_forward: all four outputs required");
   if (b == 0) return PCR_OK;
   hipStream_t st = as_stream(stream);
+  KnnIO io;
+  io.dist1 = dist1, io.idx1 = idx1, io.dist2 = dist2, io.idx2 = idx2;
   if (c == 3 && n > 0 && m > 0 &&
-      knn_spatial(xyz1, xyz2, b, n, m, k, dist1, idx1, dist2, idx2, nullptr, nullptr, 0, nullptr,
-                  workspace, workspace_bytes, xyz1 == xyz2 && n == m, st) == PCR_OK)
+      knn_spatial(xyz1, xyz2, b, n, m, k, io, workspace, workspace_bytes, xyz1 == xyz2 && n == m,
+                  st) == PCR_OK)
     return launch_status("knn_forward");
   if (c <= kMaxC && k <= 128) {
     if (n > 0) launch_knn<false>(xyz1, xyz2, b, c, n, m, k, dist1, idx1, nullptr, 0, nullptr, st);
@@ -1153,8 +1145,11 @@ extern "C" pcr_status pcr_knn_local_ppf(const float* xyz, const float* normals, 
   PCR_REQUIRE(b >= 0 && n >= 1 && k >= 1 && k <= 128, "knn_local_ppf: invalid sizes (k<=128)");
   PCR_REQUIRE(ppf != nullptr && idx != nullptr, "knn_local_ppf: idx and ppf outputs required");
   if (b == 0) return PCR_OK;
-  if (knn_spatial(xyz, xyz, b, n, n, k, dist, idx, nullptr, nullptr, normals, normals, relative,
-                  ppf, workspace, workspace_bytes, true, as_stream(stream)) == PCR_OK)
+  KnnIO io;
+  io.dist1 = dist, io.idx1 = idx, io.ppf1 = ppf;
+  io.nrm1 = io.nrm2 = normals, io.relative = relative;
+  if (knn_spatial(xyz, xyz, b, n, n, k, io, workspace, workspace_bytes, true,
+                  as_stream(stream)) == PCR_OK)
     return launch_status("knn_local_ppf");
   launch_knn<true>(xyz, xyz, b, 3, n, n, k, dist, idx, normals, relative, ppf, as_stream(stream));
   return launch_status("knn_local_ppf");
@@ -1164,9 +1159,8 @@ extern "C" pcr_status pcr_knn_prepare(const float* xyz, int b, int n, void* work
                                       size_t workspace_bytes, void* stream) {
   PCR_REQUIRE(b >= 0 && n >= 1, "knn_prepare: invalid sizes");
   if (b == 0) return PCR_OK;
-  const pcr_status rc = knn_spatial(xyz, xyz, b, n, n, 1, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, 0, nullptr, workspace, workspace_bytes, true,
-                                    as_stream(stream), 1);
+  const pcr_status rc = knn_spatial(xyz, xyz, b, n, n, 1, KnnIO{}, workspace, workspace_bytes,
+                                    true, as_stream(stream), kKnnSort);
   if (rc == PCR_ERR_UNSUPPORTED) {
     set_error("knn_prepare: no sorted path for n=%d (use pcr_knn_local_ppf)", n);
     return rc;
@@ -1182,9 +1176,11 @@ extern "C" pcr_status pcr_knn_local_ppf_prepared(const float* xyz, const float* 
               "knn_local_ppf_prepared: invalid sizes (k<=128)");
   PCR_REQUIRE(idx != nullptr, "knn_local_ppf_prepared: idx required");
   if (b == 0) return PCR_OK;
-  const pcr_status rc = knn_spatial(xyz, xyz, b, n, n, k, dist, idx, nullptr, nullptr, normals,
-                                    normals, relative, ppf, const_cast<void*>(workspace),
-                                    workspace_bytes, true, as_stream(stream), 2);
+  KnnIO io;
+  io.dist1 = dist, io.idx1 = idx, io.ppf1 = ppf;
+  io.nrm1 = io.nrm2 = normals, io.relative = relative;
+  const pcr_status rc = knn_spatial(xyz, xyz, b, n, n, k, io, const_cast<void*>(workspace),
+                                    workspace_bytes, true, as_stream(stream), kKnnSelect);
   if (rc == PCR_ERR_UNSUPPORTED) {
     set_error("knn_local_ppf_prepared: no sorted path for n=%d, k=%d", n, k);
     return rc;
@@ -1192,13 +1188,6 @@ extern "C" pcr_status pcr_knn_local_ppf_prepared(const float* xyz, const float* 
   return launch_status("knn_local_ppf_prepared");
 }
 
-// Selection + local PPF of a prepared (sorted) workspace with the neighbour
-// ids passed in sorted query order (knn_spatial stage 4): the selection
-// writes whole rows of the workspace, the PPF kernel reads them back through
-// the sort's inverse permutation and writes knn_idx [b,k,n] in original
-// order together with the PPF [b,4,k,n].  Shapes outside that path (k > 32,
-// clouds of more than 2048 points, no sorted views) take the two calls it
-// replaces, with the same outputs.
 // The two launches of pcr_knn_select_ppf as entry points of their own (the
 // c3 bench times the selection in step between them).  select_sorted returns
 // PCR_ERR_UNSUPPORTED, launching nothing, when the sorted-rows path does not
@@ -1214,9 +1203,8 @@ extern "C" pcr_status pcr_knn_select_sorted(const float* xyz, int b, int n, int 
   if (workspace == nullptr || n > kPpfSelfMaxN ||
       !knn_sorted_views(const_cast<void*>(workspace), b, n, &sidx, &inv, &npad))
     return PCR_ERR_UNSUPPORTED;
-  return knn_spatial(xyz, xyz, b, n, n, k, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     0, nullptr, const_cast<void*>(workspace), workspace_bytes, true,
-                     as_stream(stream), 2 | 4);
+  return knn_spatial(xyz, xyz, b, n, n, k, KnnIO{}, const_cast<void*>(workspace), workspace_bytes,
+                     true, as_stream(stream), kKnnSelect | kKnnSortedRows);
 }
 
 extern "C" pcr_status pcr_knn_ppf_sorted(const float* xyz, const float* normals, int b, int n,
@@ -1263,29 +1251,33 @@ extern "C" pcr_status pcr_knn_ppf_sorted(const float* xyz, const float* normals,
   return launch_status("knn_ppf_sorted");
 }
 
-// Selection + local PPF of a prepared (sorted) workspace with the neighbour
-// ids passed in sorted query order (knn_spatial stage 4): the selection
-// writes whole rows of the workspace, the PPF kernel reads them back through
-// the sort's inverse permutation and writes knn_idx [b,k,n] in original
-// order together with the PPF [b,4,k,n].  Shapes outside that path (k > 32,
-// clouds of more than 2048 points, no sorted views) take the two calls it
-// replaces, with the same outputs.
-extern "C" pcr_status pcr_knn_select_ppf(const float* xyz, const float* normals, int b, int n,
-                                         int k, int relative, int* idx, float* ppf,
-                                         const void* workspace, size_t workspace_bytes,
-                                         void* stream) {
+// The one ladder of selection + local PPF from a prepared workspace
+// (common.hpp): the sorted-rows pair when distances are not wanted and it
+// applies, else prepared selection + the PPF launch.
+pcr_status pcr::knn_select_ppf_prepared(const float* xyz, const float* normals, int b, int n, int k,
+                                        int relative, int* idx, float* dist, float* ppf,
+                                        const void* workspace, size_t workspace_bytes,
+                                        void* stream) {
   PCR_REQUIRE(b >= 0 && n >= 1 && k >= 1 && k <= 128, "knn_select_ppf: invalid sizes (k<=128)");
   PCR_REQUIRE(idx != nullptr && ppf != nullptr, "knn_select_ppf: idx and ppf required");
   if (b == 0) return PCR_OK;
-  const pcr_status rs = pcr_knn_select_sorted(xyz, b, n, k, workspace, workspace_bytes, stream);
-  if (rs == PCR_OK)
+  if (dist == nullptr &&
+      pcr_knn_select_sorted(xyz, b, n, k, workspace, workspace_bytes, stream) == PCR_OK)
     return pcr_knn_ppf_sorted(xyz, normals, b, n, k, relative, idx, ppf, workspace,
                               workspace_bytes, stream);
-  const pcr_status rc = pcr_knn_local_ppf_prepared(xyz, normals, b, n, k, relative, idx, nullptr,
+  const pcr_status rc = pcr_knn_local_ppf_prepared(xyz, normals, b, n, k, relative, idx, dist,
                                                    nullptr, workspace, workspace_bytes, stream);
   if (rc != PCR_OK) return rc;
   return pcr_local_ppf_forward(xyz, normals, xyz, normals, idx, b, n, n, k, 1, relative, ppf,
                                stream);
+}
+
+extern "C" pcr_status pcr_knn_select_ppf(const float* xyz, const float* normals, int b, int n,
+                                         int k, int relative, int* idx, float* ppf,
+                                         const void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  return knn_select_ppf_prepared(xyz, normals, b, n, k, relative, idx, nullptr, ppf, workspace,
+                                 workspace_bytes, stream);
 }
 
 extern "C" pcr_status pcr_spherical_ppf_forward(const float* coords, const float* center,

@@ -1871,19 +1871,75 @@ static size_t grid_smem_bytes(int G, int n, int nw) {
   return ((size_t)G * n + (size_t)G * (n + 1) + (n + 1) + 2 * (size_t)nw) * 4;
 }
 
-// Launch helpers.  `what`: 1 = prep only, 2 = grid only, 3 = both.
+// One launcher per kernel: each holds that kernel's launch geometry and LDS
+// size once; the entry points below validate and call them.
+enum VoxPart : int { kVoxPrep = 1, kVoxGrid = 2, kVoxDevox = 4 };
+
+// What run_voxelize writes; anything may stay null where the parts run do
+// not produce it.
+struct VoxOut {
+  float* grid = nullptr;  // [b,c,r^3] voxel means
+  int* ind = nullptr;     // [b,n]
+  int* cnt = nullptr;     // [b,r^3]
+  float* norm = nullptr;  // [b,3,n] normalised coords (kSphNormalize)
+  float* devox = nullptr; // [b,c,n]
+  int* dinds = nullptr;   // [b,8,n] devox corners: written by prep, read by devox
+  float* dwgts = nullptr; // [b,8,n]
+  float* desc = nullptr;  // [b,c]
+};
+
+template <int MODE, int NT>
+static pcr_status launch_prep(const float* coords_f, const int* coords_i, int b, int n, int r,
+                              const VoxWs& ws, const VoxOut& o, hipStream_t stream,
+                              const char* name) {
+  const int npad = next_pow2(n < NT ? NT : n);
+  const size_t smem = (size_t)npad * 8 + (size_t)ws.W * 8 + (size_t)n * 8;
+  PCR_REQUIRE(smem <= 150 * 1024, "%s: prep LDS %zu too large", name, smem);
+  allow_big_lds(vox_prep_kernel<MODE, NT>, smem);
+  hipLaunchKernelGGL((vox_prep_kernel<MODE, NT>), dim3(b), dim3(NT), smem, stream, coords_f,
+                     coords_i, n, r, npad, o.norm, o.ind, ws, o.dinds, o.dwgts, 1);
+  return PCR_OK;
+}
+
+// vox_grid_kernel<PART, NT, MG>: PART 1 = dense grid + cnt (the only part
+// that may be tiled over r^3), 2 = devox + descriptor, 3 = both from the same
+// LDS means; at most MG channels per workgroup.
+template <int PART, int NT, int MG>
+static pcr_status launch_grid(const float* features, int b, int c, int n, int r3, const VoxWs& ws,
+                              const VoxOut& o, hipStream_t stream, const char* name) {
+  // one tile covers the whole grid when its bitmap fits comfortably
+  const int tile = r3 <= 65536 ? ((r3 + 31) / 32) * 32 : 32768;
+  const int ntiles = ceil_div(r3, tile);
+  const int nw = (tile + 31) / 32 + 1;
+  if (PART & 2) {
+    PCR_REQUIRE(ntiles == 1, "%s: fused devoxelisation needs r^3 <= 65536", name);
+    PCR_REQUIRE(c > 0, "%s: fused devoxelisation needs c > 0", name);
+  }
+  int G = 1;
+  const int ngrp = c > 0 ? pick_groups(c, n, MG, &G) : 1;
+  const size_t smem = grid_smem_bytes(G, n, nw);
+  PCR_REQUIRE(smem <= 150 * 1024, "%s: grid LDS %zu too large", name, smem);
+  allow_big_lds(vox_grid_kernel<PART, NT, MG>, smem);
+  hipLaunchKernelGGL((vox_grid_kernel<PART, NT, MG>), dim3(ntiles * ngrp * b), dim3(NT), smem,
+                     stream, features, c, n, r3, G, tile, ws, (PART & 1) ? o.grid : nullptr,
+                     (PART & 1) ? o.cnt : nullptr, (PART & 2) ? o.dinds : nullptr,
+                     (PART & 2) ? o.dwgts : nullptr, (PART & 2) ? o.devox : nullptr,
+                     (PART & 2) ? o.desc : nullptr, ntiles, ngrp, ntiles * ngrp * b);
+  return PCR_OK;
+}
+
 template <int MODE>
 static pcr_status run_voxelize(const float* features, const float* coords_f, const int* coords_i,
-                               int b, int c, int n, int r, float* out, int* ind, int* cnt,
-                               void* workspace, size_t ws_bytes, hipStream_t stream,
-                               float* norm_out, float* devox, int* dinds, float* dwgts,
-                               float* desc, const char* name, int what = 3) {
+                               int b, int c, int n, int r, const VoxOut& o, void* workspace,
+                               size_t ws_bytes, hipStream_t stream, const char* name,
+                               int parts = kVoxPrep | kVoxGrid) {
   PCR_REQUIRE(b >= 0 && c >= 0 && n >= 0 && r >= 1, "%s: invalid sizes b=%d c=%d n=%d r=%d", name,
               b, c, n, r);
   PCR_REQUIRE((int64_t)r * r * r <= (1 << 24), "%s: resolution %d too large", name, r);
   if (b == 0) return PCR_OK;
-  if (n > kMaxSortN && MODE != kSphNormalize && what == 3 && devox == nullptr)
-    return run_voxelize_big<MODE>(features, coords_f, coords_i, b, c, n, r, out, ind, cnt,
+  if (n > kMaxSortN && MODE != kSphNormalize && parts == (kVoxPrep | kVoxGrid) &&
+      o.devox == nullptr)
+    return run_voxelize_big<MODE>(features, coords_f, coords_i, b, c, n, r, o.grid, o.ind, o.cnt,
                                   workspace, ws_bytes, stream, name);
   PCR_REQUIRE(n >= 1 && n <= kMaxSortN,
               "%s: n=%d points per cloud unsupported on this path (1..%d)", name, n, kMaxSortN);
@@ -1893,7 +1949,8 @@ static pcr_status run_voxelize(const float* features, const float* coords_f, con
   PCR_REQUIRE(workspace != nullptr && ws_bytes >= need, "%s: workspace too small (%zu < %zu)",
               name, ws_bytes, need);
   PCR_PRIO_INIT();
-  if (what & 1) {
+  pcr_status rc = PCR_OK;
+  if (parts & kVoxPrep) {
     // clouds of <= 1024 points: a 256- or 512-thread workgroup rather than
     // 1024, so a prep workgroup fits on a CU beside the other queues'
     // kernels instead of waiting for whole CUs to drain.  257..1024 points:
@@ -1901,75 +1958,28 @@ static pcr_status run_voxelize(const float* features, const float* coords_f, con
     // kernel heads the critical voxel chain, c2 379-385k -> 385-394k
     // clouds/s against 256 threads (3 interleaved rounds,
     // profiles/r04_ab_prep.log); 1024 threads measured between the two
-    const bool small = n <= kSmallPrepN;
-    const int nt = small ? kSmallPrepThreads : kPrepThreads;
-    const int npad = next_pow2(n < nt ? nt : n);
-    size_t prep_smem = (size_t)npad * 8 + (size_t)ws.W * 8 + (size_t)n * 8;
-    PCR_REQUIRE(prep_smem <= 150 * 1024, "%s: prep LDS %zu too large", name, prep_smem);
-    if (small && n > 256) {
-      const int npad5 = next_pow2(n < 512 ? 512 : n);
-      const size_t sm5 = (size_t)npad5 * 8 + (size_t)ws.W * 8 + (size_t)n * 8;
-      allow_big_lds(vox_prep_kernel<MODE, 512>, sm5);
-      hipLaunchKernelGGL((vox_prep_kernel<MODE, 512>), dim3(b), dim3(512), sm5, stream, coords_f,
-                         coords_i, n, r, npad5, norm_out, ind, ws, dinds, dwgts, 1);
-    } else if (small) {
-      allow_big_lds(vox_prep_kernel<MODE, kSmallPrepThreads>, prep_smem);
-      hipLaunchKernelGGL((vox_prep_kernel<MODE, kSmallPrepThreads>), dim3(b),
-                         dim3(kSmallPrepThreads), prep_smem, stream, coords_f, coords_i, n, r,
-                         npad, norm_out, ind, ws, dinds, dwgts, 1);
-    } else {
-      const int npad1 = next_pow2(n < kPrepThreads ? kPrepThreads : n);
-      const size_t sm1 = (size_t)npad1 * 8 + (size_t)ws.W * 8 + (size_t)n * 8;
-      allow_big_lds(vox_prep_kernel<MODE, kPrepThreads>, sm1);
-      hipLaunchKernelGGL((vox_prep_kernel<MODE, kPrepThreads>), dim3(b), dim3(kPrepThreads),
-                         sm1, stream, coords_f, coords_i, n, r, npad1, norm_out, ind, ws,
-                         dinds, dwgts, 1);
-    }
+    if (n <= kSmallPrepThreads)
+      rc = launch_prep<MODE, kSmallPrepThreads>(coords_f, coords_i, b, n, r, ws, o, stream, name);
+    else if (n <= kSmallPrepN)
+      rc = launch_prep<MODE, 512>(coords_f, coords_i, b, n, r, ws, o, stream, name);
+    else
+      rc = launch_prep<MODE, kPrepThreads>(coords_f, coords_i, b, n, r, ws, o, stream, name);
+    if (rc != PCR_OK) return rc;
   }
-  const bool do_grid = (what & 2) != 0;
-  const bool do_dev = (what & 4) != 0 && devox != nullptr;
-  // one tile covers the whole grid when its bitmap fits comfortably
-  const int tile = r3 <= 65536 ? ((r3 + 31) / 32) * 32 : 32768;
-  const int ntiles = ceil_div(r3, tile);
-  const int nw = (tile + 31) / 32 + 1;
-  if (do_dev) {
-    PCR_REQUIRE(ntiles == 1, "%s: fused devoxelisation needs r^3 <= 65536", name);
-    PCR_REQUIRE(c > 0, "%s: fused devoxelisation needs c > 0", name);
-  }
-  if (do_grid && do_dev) {
+  const bool do_grid = (parts & kVoxGrid) != 0;
+  const bool do_dev = (parts & kVoxDevox) != 0 && o.devox != nullptr;
+  if (do_grid && do_dev)
     // streaming + devox from the same LDS means: two channels per workgroup
     // as in the streaming-only part; the devox tail gathers by prep's
     // corner -> segment map
-    int G = 1;
-    const int ngrp = pick_groups(c, n, 2, &G);
-    const size_t smem = grid_smem_bytes(G, n, nw);
-    PCR_REQUIRE(smem <= 150 * 1024, "%s: grid LDS %zu too large", name, smem);
-    allow_big_lds(vox_grid_kernel<3, kGridThreads, 2>, smem);
-    hipLaunchKernelGGL((vox_grid_kernel<3, kGridThreads, 2>), dim3(ngrp * b),
-                       dim3(kGridThreads), smem, stream, features, c, n, r3, G, tile, ws, out, cnt,
-                       dinds, dwgts, devox, desc, 1, ngrp, ngrp * b);
-  } else if (do_dev) {
-    int G = 1;
-    const int ngrp = pick_groups(c, n, 4, &G);
-    const size_t smem = grid_smem_bytes(G, n, nw);
-    PCR_REQUIRE(smem <= 150 * 1024, "%s: grid LDS %zu too large", name, smem);
-    allow_big_lds(vox_grid_kernel<2, kDevoxThreads, 4>, smem);
-    hipLaunchKernelGGL((vox_grid_kernel<2, kDevoxThreads, 4>), dim3(ngrp * b),
-                       dim3(kDevoxThreads), smem, stream, features, c, n, r3, G, tile, ws, nullptr,
-                       nullptr, dinds, dwgts, devox, desc, 1, ngrp, ngrp * b);
-  } else if (do_grid && (c > 0 || cnt)) {
+    rc = launch_grid<3, kGridThreads, 2>(features, b, c, n, r3, ws, o, stream, name);
+  else if (do_dev)
+    rc = launch_grid<2, kDevoxThreads, 4>(features, b, c, n, r3, ws, o, stream, name);
+  else if (do_grid && (c > 0 || o.cnt))
     // streaming part: two channels per workgroup keep its LDS small (~29 KB
     // at n = 1024), so its workgroups fit beside the KNN selection's
-    int G = 1;
-    const int ngrp = c > 0 ? pick_groups(c, n, 2, &G) : 1;
-    const size_t smem = grid_smem_bytes(G, n, nw);
-    PCR_REQUIRE(smem <= 150 * 1024, "%s: grid LDS %zu too large", name, smem);
-    allow_big_lds(vox_grid_kernel<1, kGridThreads, 2>, smem);
-    hipLaunchKernelGGL((vox_grid_kernel<1, kGridThreads, 2>),
-                       dim3(ntiles * ngrp * b), dim3(kGridThreads), smem, stream,
-                       features, c, n, r3, G, tile, ws, out, cnt, nullptr, nullptr, nullptr,
-                       nullptr, ntiles, ngrp, ntiles * ngrp * b);
-  }
+    rc = launch_grid<1, kGridThreads, 2>(features, b, c, n, r3, ws, o, stream, name);
+  if (rc != PCR_OK) return rc;
   return launch_status(name);
 }
 
@@ -1993,18 +2003,21 @@ extern "C" pcr_status pcr_spherical_avg_voxelize_forward(const float* features, 
                                                          int b, int c, int n, int r, float* out,
                                                          int* ind, int* cnt, void* workspace,
                                                          size_t workspace_bytes, void* stream) {
-  return run_voxelize<kSphCoords>(features, coords, nullptr, b, c, n, r, out, ind, cnt, workspace,
-                                  workspace_bytes, as_stream(stream), nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, "spherical_avg_voxelize_forward");
+  VoxOut o;
+  o.grid = out, o.ind = ind, o.cnt = cnt;
+  return run_voxelize<kSphCoords>(features, coords, nullptr, b, c, n, r, o, workspace,
+                                  workspace_bytes, as_stream(stream),
+                                  "spherical_avg_voxelize_forward");
 }
 
 extern "C" pcr_status pcr_avg_voxelize_forward(const float* features, const int* coords, int b,
                                                int c, int n, int r, float* out, int* ind, int* cnt,
                                                void* workspace, size_t workspace_bytes,
                                                void* stream) {
-  return run_voxelize<kCube>(features, nullptr, coords, b, c, n, r, out, ind, cnt, workspace,
-                             workspace_bytes, as_stream(stream), nullptr, nullptr, nullptr,
-                             nullptr, nullptr, "avg_voxelize_forward");
+  VoxOut o;
+  o.grid = out, o.ind = ind, o.cnt = cnt;
+  return run_voxelize<kCube>(features, nullptr, coords, b, c, n, r, o, workspace, workspace_bytes,
+                             as_stream(stream), "avg_voxelize_forward");
 }
 
 extern "C" pcr_status pcr_avg_voxelize_backward(const float* grad_y, const int* ind,
@@ -2058,51 +2071,49 @@ static pcr_status extractor_ws(int b, int c, int n, int r, void* workspace, size
   return PCR_OK;
 }
 
+// vox_means_kernel<2, NT, DEVOX>: 2 channels per workgroup (~24 KB of LDS, so
+// it fits beside the KNN selection's workgroups); clouds of more than 1024
+// points (c3: 2048): 512 threads, the same four points per thread (4 or 8
+// channels per workgroup measured +1% / -2% in the c2 step).
+// n <= kMeansMaxN.
+template <bool DEVOX>
+static void launch_means(const float* features, int b, int c, int n, const VoxWs& ws,
+                         const float* dwgts, float* devox, float* desc, hipStream_t stream) {
+  PCR_PRIO_INIT();
+  const int ngrp = ceil_div(c, 2);
+  const size_t smem = ((size_t)2 * n + (size_t)2 * (n + 1) + n + (n + 1)) * 4;
+  auto launch = [&](auto kernel, int nt) {
+    allow_big_lds(kernel, smem);
+    hipLaunchKernelGGL(kernel, dim3(ngrp * b), dim3(nt), smem, stream, features, c, n, ws, dwgts,
+                       devox, desc, ngrp);
+  };
+  if (n > kMeansPB * kMeansNT) launch(vox_means_kernel<2, 2 * kMeansNT, DEVOX>, 2 * kMeansNT);
+  else launch(vox_means_kernel<2, kMeansNT, DEVOX>, kMeansNT);
+}
+
 extern "C" pcr_status pcr_extractor_voxel_means_devox(const float* features, int b, int c, int n,
                                                       int r, float* devox, const int* dinds,
                                                       const float* dwgts, float* desc,
                                                       void* workspace, size_t workspace_bytes,
                                                       void* stream) {
   const char* name = "extractor_voxel_means_devox";
-  PCR_PRIO_INIT();
   VoxWs ws;
   pcr_status rc = extractor_ws(b, c, n, r, workspace, workspace_bytes, &ws, name);
   if (rc != PCR_OK) return rc;
   PCR_REQUIRE(devox != nullptr && dinds != nullptr && dwgts != nullptr,
               "%s: devox, dinds, dwgts required", name);
   if (b == 0) return PCR_OK;
-  const int r3 = r * r * r;
-  const int tile = ((r3 + 31) / 32) * 32;
-  const int nw = tile / 32 + 1;
   if (n <= kMeansMaxN) {
-    // 2 channels per workgroup (~24 KB of LDS, so it fits beside the KNN
-    // selection's workgroups); clouds of more than 1024 points (c3: 2048):
-    // 512 threads, the same four points per thread (4 or 8 channels per
-    // workgroup measured +1% / -2% in the c2 step)
-    const int nt = n > kMeansPB * kMeansNT ? 2 * kMeansNT : kMeansNT;
-    const int ngrp = ceil_div(c, 2);
-    const size_t smem = ((size_t)2 * n + (size_t)2 * (n + 1) + n + (n + 1)) * 4;
-    if (nt == kMeansNT) {
-      allow_big_lds(vox_means_kernel<2, kMeansNT>, smem);
-      hipLaunchKernelGGL((vox_means_kernel<2, kMeansNT>), dim3(ngrp * b), dim3(kMeansNT), smem,
-                         as_stream(stream), features, c, n, ws, dwgts, devox, desc, ngrp);
-    } else {
-      allow_big_lds(vox_means_kernel<2, 2 * kMeansNT>, smem);
-      hipLaunchKernelGGL((vox_means_kernel<2, 2 * kMeansNT>), dim3(ngrp * b), dim3(2 * kMeansNT),
-                         smem, as_stream(stream), features, c, n, ws, dwgts, devox, desc, ngrp);
-    }
+    launch_means<true>(features, b, c, n, ws, dwgts, devox, desc, as_stream(stream));
     return launch_status(name);
   }
   // larger clouds: the grid kernel's devox part (means formed per workgroup)
-  int G = 1;
-  const int ngrp = pick_groups(c, n, 2, &G);
-  const size_t smem = grid_smem_bytes(G, n, nw);
-  PCR_REQUIRE(smem <= 150 * 1024, "%s: LDS %zu too large", name, smem);
-  allow_big_lds(vox_grid_kernel<2, 256, 2>, smem);
-  hipLaunchKernelGGL((vox_grid_kernel<2, 256, 2>), dim3(ngrp * b), dim3(256), smem,
-                     as_stream(stream), features, c, n, r3, G, tile, ws, nullptr, nullptr, dinds,
-                     dwgts, devox, desc, 1, ngrp, ngrp * b);
-  return launch_status(name);
+  PCR_PRIO_INIT();
+  VoxOut o;
+  o.devox = devox, o.desc = desc;
+  o.dinds = const_cast<int*>(dinds), o.dwgts = const_cast<float*>(dwgts);
+  rc = launch_grid<2, 256, 2>(features, b, c, n, r * r * r, ws, o, as_stream(stream), name);
+  return rc != PCR_OK ? rc : launch_status(name);
 }
 
 static int device_cus() {
@@ -2117,20 +2128,17 @@ static int device_cus() {
   return cus;
 }
 
-extern "C" pcr_status pcr_extractor_voxel_stream(int b, int c, int n, int r, int* cnt,
-                                                 float* grid, void* workspace,
-                                                 size_t workspace_bytes, void* stream) {
-  const char* name = "extractor_voxel_stream";
+// vox_stream_kernel: the dense grid + cnt from the workspace means and, with
+// `devox` (clouds of <= kStreamDvMaxN points), devox + descriptor from the
+// same means in LDS (dwgts / devox / desc, else all three null).
+static pcr_status launch_stream(int b, int c, int n, int r3, const VoxWs& ws, int* cnt,
+                                float* grid, const float* dwgts, float* devox, float* desc,
+                                hipStream_t stream, const char* name) {
   PCR_PRIO_INIT();
-  VoxWs ws;
-  pcr_status rc = extractor_ws(b, c, n, r, workspace, workspace_bytes, &ws, name);
-  if (rc != PCR_OK) return rc;
-  PCR_REQUIRE(grid != nullptr, "%s: grid required", name);
-  if (b == 0) return PCR_OK;
-  const int r3 = r * r * r;
-  PCR_REQUIRE(n <= kStreamMaxN && r3 <= 32 * kStreamMaxW && r3 % 128 == 0,
-              "%s: n=%d r=%d unsupported (n <= %d, r^3 <= %d, r^3 %% 128 == 0)", name, n, r,
-              kStreamMaxN, 32 * kStreamMaxW);
+  PCR_REQUIRE(n <= (devox ? kStreamDvMaxN : kStreamMaxN) && r3 <= 32 * kStreamMaxW &&
+                  r3 % 128 == 0,
+              "%s: n=%d r^3=%d unsupported (n <= %d, r^3 <= %d, r^3 %% 128 == 0)", name, n, r3,
+              devox ? kStreamDvMaxN : kStreamMaxN, 32 * kStreamMaxW);
   // two channels per item and three means buffers: 36 KB, so the grid
   // kernel fits on a CU beside two selection workgroups (four channels per
   // item measured ~3% slower in the step despite half the index work per
@@ -2142,23 +2150,34 @@ extern "C" pcr_status pcr_extractor_voxel_stream(int b, int c, int n, int r, int
   const int ngrp = ceil_div(c, G);
   // a few workgroups per cloud (about one per CU in all), each a contiguous
   // range of channel-group items of that cloud
-  int wpc = device_cus() / (b > 0 ? b : 1);
+  int wpc = device_cus() / b;
   if (wpc < 1) wpc = 1;
   if (wpc > ngrp) wpc = ngrp;
   const int per = ceil_div(ngrp, wpc);
   PCR_REQUIRE(ws.W % 64 == 0, "%s: r^3 %% 2048 != 0 unsupported", name);
   const size_t smem = stream_smem_bytes(NGP, ws.W, ws.ms);
-#define PCR_LAUNCH_STREAM(NGV)                                                                 \
-  do {                                                                                        \
-    allow_big_lds(vox_stream_kernel<4, kStreamNB, 2, 16, G, NGV>, smem);                      \
-    hipLaunchKernelGGL((vox_stream_kernel<4, kStreamNB, 2, 16, G, NGV>), dim3(b * wpc),       \
-                       dim3(5 * 64), smem, as_stream(stream), c, n, r3, ws, grid, cnt, ngrp,   \
-                       wpc, per, nullptr, nullptr, nullptr);                                  \
-  } while (0)
-  if (wide) PCR_LAUNCH_STREAM(17);
-  else PCR_LAUNCH_STREAM(kStreamNG);
-#undef PCR_LAUNCH_STREAM
+  auto launch = [&](auto kernel) {
+    allow_big_lds(kernel, smem);
+    hipLaunchKernelGGL(kernel, dim3(b * wpc), dim3(5 * 64), smem, stream, c, n, r3, ws, grid, cnt,
+                       ngrp, wpc, per, dwgts, devox, desc);
+  };
+  if (devox) launch(vox_stream_kernel<4, kStreamNB, 2, 16, G, kStreamNG, kStreamDvMaxN>);
+  else if (wide) launch(vox_stream_kernel<4, kStreamNB, 2, 16, G, 17>);
+  else launch(vox_stream_kernel<4, kStreamNB, 2, 16, G, kStreamNG>);
   return launch_status(name);
+}
+
+extern "C" pcr_status pcr_extractor_voxel_stream(int b, int c, int n, int r, int* cnt,
+                                                 float* grid, void* workspace,
+                                                 size_t workspace_bytes, void* stream) {
+  const char* name = "extractor_voxel_stream";
+  VoxWs ws;
+  pcr_status rc = extractor_ws(b, c, n, r, workspace, workspace_bytes, &ws, name);
+  if (rc != PCR_OK) return rc;
+  PCR_REQUIRE(grid != nullptr, "%s: grid required", name);
+  if (b == 0) return PCR_OK;
+  return launch_stream(b, c, n, r * r * r, ws, cnt, grid, nullptr, nullptr, nullptr,
+                       as_stream(stream), name);
 }
 
 // The voxel stage's back half with the devox inside the grid stream
@@ -2183,20 +2202,7 @@ extern "C" pcr_status pcr_extractor_voxel_means(const float* features, int b, in
   PCR_REQUIRE(features != nullptr && n <= kMeansMaxN, "%s: features required, n <= %d", name,
               kMeansMaxN);
   if (b == 0) return PCR_OK;
-  const int ngrp = ceil_div(c, 2);
-  const size_t smem = ((size_t)2 * n + (size_t)2 * (n + 1) + n + (n + 1)) * 4;
-  // clouds of more than 1024 points: 512 threads, the same four points per thread
-  if (n > kMeansPB * kMeansNT) {
-    allow_big_lds(vox_means_kernel<2, 2 * kMeansNT, false>, smem);
-    hipLaunchKernelGGL((vox_means_kernel<2, 2 * kMeansNT, false>), dim3(ngrp * b),
-                       dim3(2 * kMeansNT), smem, as_stream(stream), features, c, n, ws, nullptr,
-                       nullptr, nullptr, ngrp);
-  } else {
-    allow_big_lds(vox_means_kernel<2, kMeansNT, false>, smem);
-    hipLaunchKernelGGL((vox_means_kernel<2, kMeansNT, false>), dim3(ngrp * b), dim3(kMeansNT),
-                       smem, as_stream(stream), features, c, n, ws, nullptr, nullptr, nullptr,
-                       ngrp);
-  }
+  launch_means<false>(features, b, c, n, ws, nullptr, nullptr, nullptr, as_stream(stream));
   return launch_status(name);
 }
 
@@ -2214,21 +2220,8 @@ extern "C" pcr_status pcr_extractor_voxel_stream_devox(int b, int c, int n, int 
   PCR_REQUIRE(pcr_extractor_stream_devox_ok(n, c, r), "%s: n=%d c=%d r=%d unsupported", name, n,
               c, r);
   if (b == 0) return PCR_OK;
-  const int r3 = r * r * r;
-  constexpr int G = kStreamG;
-  const int NGP = kStreamNG;
-  PCR_REQUIRE(G * ws.ms * 4 <= NGP * 1024, "%s: means rows too long", name);
-  const int ngrp = ceil_div(c, G);
-  int wpc = device_cus() / b;
-  if (wpc < 1) wpc = 1;
-  if (wpc > ngrp) wpc = ngrp;
-  const int per = ceil_div(ngrp, wpc);
-  const size_t smem = stream_smem_bytes(NGP, ws.W, ws.ms);
-  allow_big_lds(vox_stream_kernel<4, kStreamNB, 2, 16, G, kStreamNG, kStreamDvMaxN>, smem);
-  hipLaunchKernelGGL((vox_stream_kernel<4, kStreamNB, 2, 16, G, kStreamNG, kStreamDvMaxN>),
-                     dim3(b * wpc), dim3(5 * 64), smem, as_stream(stream), c, n, r3, ws, grid, cnt,
-                     ngrp, wpc, per, dwgts, devox, desc);
-  return launch_status(name);
+  return launch_stream(b, c, n, r * r * r, ws, cnt, grid, dwgts, devox, desc, as_stream(stream),
+                       name);
 }
 
 extern "C" pcr_status pcr_extractor_voxel_prep(const float* xyz, int b, int n, int r,
@@ -2237,18 +2230,22 @@ extern "C" pcr_status pcr_extractor_voxel_prep(const float* xyz, int b, int n, i
                                                size_t workspace_bytes, void* stream) {
   PCR_REQUIRE(ind != nullptr && dinds != nullptr && dwgts != nullptr,
               "extractor_voxel_prep: ind, dinds, dwgts required");
-  return run_voxelize<kSphNormalize>(nullptr, xyz, nullptr, b, 0, n, r, nullptr, ind, nullptr,
-                                     workspace, workspace_bytes, as_stream(stream), norm_coords,
-                                     nullptr, dinds, dwgts, nullptr, "extractor_voxel_prep", 1);
+  VoxOut o;
+  o.norm = norm_coords, o.ind = ind, o.dinds = dinds, o.dwgts = dwgts;
+  return run_voxelize<kSphNormalize>(nullptr, xyz, nullptr, b, 0, n, r, o, workspace,
+                                     workspace_bytes, as_stream(stream), "extractor_voxel_prep",
+                                     kVoxPrep);
 }
 
 extern "C" pcr_status pcr_extractor_voxel_grid(const float* features, int b, int c, int n, int r,
                                                int* cnt, float* grid, void* workspace,
                                                size_t workspace_bytes, void* stream) {
   PCR_REQUIRE(grid != nullptr, "extractor_voxel_grid: grid required");
-  return run_voxelize<kSphNormalize>(features, nullptr, nullptr, b, c, n, r, grid, nullptr, cnt,
-                                     workspace, workspace_bytes, as_stream(stream), nullptr,
-                                     nullptr, nullptr, nullptr, nullptr, "extractor_voxel_grid", 2);
+  VoxOut o;
+  o.grid = grid, o.cnt = cnt;
+  return run_voxelize<kSphNormalize>(features, nullptr, nullptr, b, c, n, r, o, workspace,
+                                     workspace_bytes, as_stream(stream), "extractor_voxel_grid",
+                                     kVoxGrid);
 }
 
 extern "C" pcr_status pcr_extractor_voxel_devox(const float* features, int b, int c, int n, int r,
@@ -2257,10 +2254,12 @@ extern "C" pcr_status pcr_extractor_voxel_devox(const float* features, int b, in
                                                 size_t workspace_bytes, void* stream) {
   PCR_REQUIRE(devox != nullptr && dinds != nullptr && dwgts != nullptr,
               "extractor_voxel_devox: devox, dinds, dwgts required");
-  return run_voxelize<kSphNormalize>(features, nullptr, nullptr, b, c, n, r, nullptr, nullptr,
-                                     nullptr, workspace, workspace_bytes, as_stream(stream), nullptr,
-                                     devox, const_cast<int*>(dinds), const_cast<float*>(dwgts),
-                                     desc, "extractor_voxel_devox", 4);
+  VoxOut o;
+  o.devox = devox, o.desc = desc;
+  o.dinds = const_cast<int*>(dinds), o.dwgts = const_cast<float*>(dwgts);
+  return run_voxelize<kSphNormalize>(features, nullptr, nullptr, b, c, n, r, o, workspace,
+                                     workspace_bytes, as_stream(stream), "extractor_voxel_devox",
+                                     kVoxDevox);
 }
 
 extern "C" pcr_status pcr_extractor_voxel_grid_devox(const float* features, int b, int c, int n,
@@ -2270,10 +2269,12 @@ extern "C" pcr_status pcr_extractor_voxel_grid_devox(const float* features, int 
                                                      size_t workspace_bytes, void* stream) {
   PCR_REQUIRE(grid != nullptr && devox != nullptr && dinds != nullptr && dwgts != nullptr,
               "extractor_voxel_grid_devox: grid, devox, dinds, dwgts required");
-  return run_voxelize<kSphNormalize>(features, nullptr, nullptr, b, c, n, r, grid, nullptr, cnt,
-                                     workspace, workspace_bytes, as_stream(stream), nullptr,
-                                     devox, const_cast<int*>(dinds), const_cast<float*>(dwgts),
-                                     desc, "extractor_voxel_grid_devox", 6);
+  VoxOut o;
+  o.grid = grid, o.cnt = cnt, o.devox = devox, o.desc = desc;
+  o.dinds = const_cast<int*>(dinds), o.dwgts = const_cast<float*>(dwgts);
+  return run_voxelize<kSphNormalize>(features, nullptr, nullptr, b, c, n, r, o, workspace,
+                                     workspace_bytes, as_stream(stream),
+                                     "extractor_voxel_grid_devox", kVoxGrid | kVoxDevox);
 }
 
 extern "C" pcr_status pcr_extractor_voxel_stage(const float* xyz, const float* features, int b,
@@ -2285,9 +2286,12 @@ extern "C" pcr_status pcr_extractor_voxel_stage(const float* xyz, const float* f
   PCR_REQUIRE(devox == nullptr || (dinds != nullptr && dwgts != nullptr),
               "extractor_voxel_stage: devox needs dinds/dwgts buffers");
   PCR_REQUIRE(desc == nullptr || devox != nullptr, "extractor_voxel_stage: desc needs devox");
-  return run_voxelize<kSphNormalize>(features, xyz, nullptr, b, c, n, r, grid, ind, cnt, workspace,
-                                     workspace_bytes, as_stream(stream), norm_coords, devox,
-                                     dinds, dwgts, desc, "extractor_voxel_stage", 7);
+  VoxOut o;
+  o.grid = grid, o.ind = ind, o.cnt = cnt, o.norm = norm_coords;
+  o.devox = devox, o.dinds = dinds, o.dwgts = dwgts, o.desc = desc;
+  return run_voxelize<kSphNormalize>(features, xyz, nullptr, b, c, n, r, o, workspace,
+                                     workspace_bytes, as_stream(stream), "extractor_voxel_stage",
+                                     kVoxPrep | kVoxGrid | kVoxDevox);
 }
 
 #ifdef PCR_DIAG

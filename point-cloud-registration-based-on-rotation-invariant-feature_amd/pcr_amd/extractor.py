@@ -12,16 +12,17 @@ features [B,C,N], all resident on the GPU):
   grid (stream B): spherical_avg_voxelize's dense grid [B,C,r^3] + cnt, then
       spherical_trilinear_devoxelize of that grid ([B,C,N] + inds/wgts) +
       per-cloud descriptor (max over points) [B,C], reading only the 80
-      corner voxels per channel every spherical corner lies in (clouds of
-      more than 4096 points: the devox re-forms the voxel means on stream C)
+      corner voxels per channel every spherical corner lies in
 
 The streams are forked from and joined back to the caller's stream.
 ``forward()`` enqueues one step from Python; ``capture()`` records one step
 into a hipGraph; ``run_native()`` has the library (pcr_extractor_run) enqueue
-S consecutive steps with no join between them on alternating buffer sets, so
-step i+1's front stages overlap step i's back stages -- the product schedule
-bench.py measures.
+S consecutive steps with no join between them, so step i+1's front stages
+overlap step i's back stages; ``run_ring()`` does the same over a ring of
+batches with one output set each, on per-queue workspaces -- the product
+schedule bench.py measures.
 """
+import collections
 import ctypes
 
 import torch
@@ -30,9 +31,13 @@ from . import _lib
 from .ops import _ptr
 
 
+# the buffers a later stage of the same step reads (SphExtractor._set)
+BufferSet = collections.namedtuple("BufferSet", "knn_ws ws dinds dwgts knn_idx")
+
+
 class SphExtractor:
     def __init__(self, batch, npoints, channels, k, resolution, device="cuda", relative=True,
-                 with_dist=False, split_ppf=True, stream_devox=True):
+                 with_dist=False, stream_devox=True):
         # stream_devox: the split voxel stage evaluates the devox inside the
         # grid stream where it applies (<= 1024 points); False keeps it in the
         # means launch, in the eager / pipelined paths and in the native
@@ -40,7 +45,6 @@ class SphExtractor:
         self.stream_devox = stream_devox
         self.b, self.n, self.c, self.k, self.r = batch, npoints, channels, k, resolution
         self.relative = relative
-        self.split_ppf = split_ppf
         self.device = torch.device(device)
         b, n, c, r = batch, npoints, channels, resolution
         r3 = r * r * r
@@ -81,11 +85,9 @@ class SphExtractor:
     # front stages while step i's back stages still read set i % 2.
     def _set(self, slot):
         if slot == 0:
-            return self.knn_ws, self.ws, self.dinds, self.dwgts, self.knn_idx
+            return BufferSet(self.knn_ws, self.ws, self.dinds, self.dwgts, self.knn_idx)
         if self._set1 is None:
-            e = torch.empty_like
-            self._set1 = (e(self.knn_ws), e(self.ws), e(self.dinds), e(self.dwgts),
-                          e(self.knn_idx))
+            self._set1 = BufferSet(*(torch.empty_like(t) for t in self._set(0)))
             self._order_new_buffers()
         return self._set1
 
@@ -120,17 +122,14 @@ class SphExtractor:
             self._order_new_buffers()
         return self._vset1
 
-    def neighbor_stage(self, xyz, normals, stream):
-        """Sort + select + PPF in one call (the eager, unsplit path)."""
-        _lib.check(_lib.load().pcr_knn_local_ppf(
-            _ptr(xyz), _ptr(normals), self.b, self.n, self.k, int(self.relative),
-            _ptr(self.knn_idx), _ptr(self.knn_dist), _ptr(self.local_ppf), _ptr(self.knn_ws),
-            self.knn_ws.numel(), stream), "knn_local_ppf")
+    def _desc(self, slot, desc):
+        """The descriptor output of a devox launch: the caller's, else slot's."""
+        return self._vset(slot)[3] if desc is None else desc
 
     def knn_sort(self, xyz, stream, slot=0):
         """Morton sort into workspace set `slot`; False when the sorted path
         does not apply (then knn_select falls back to the one-call path)."""
-        kws = self._set(slot)[0]
+        kws = self._set(slot).knn_ws
         rc = _lib.load().pcr_knn_prepare(_ptr(xyz), self.b, self.n, _ptr(kws), kws.numel(),
                                          stream)
         if rc == -3:  # PCR_ERR_UNSUPPORTED, nothing launched
@@ -138,36 +137,40 @@ class SphExtractor:
         _lib.check(rc, "knn_prepare")
         return True
 
-    def knn_select(self, xyz, normals, stream, slot=0, sorted_ok=True, ppf=True, events=None):
-        """Selection (+ local PPF unless ppf=False) into index set `slot`.
+    def knn_select(self, xyz, normals, stream, slot=0, sorted_ok=True, events=None):
+        """Selection + local PPF into index set `slot`.
         events: (ev0, ev1) torch.cuda.Events recorded on `stream` (a
         torch.cuda.Stream) around the selection launch alone."""
-        kws, idx = self._set(slot)[0], self._set(slot)[4]
-        ppf_out = self._ppf(slot)
+        lib, st = _lib.load(), self._set(slot)
         torch_stream = stream if isinstance(stream, torch.cuda.Stream) else None
         if torch_stream is not None:
             stream = torch_stream.cuda_stream
-        if torch_stream is None:
+        else:
             events = None  # events are recorded on a torch.cuda.Stream
-        if not sorted_ok:
-            _lib.check(_lib.load().pcr_knn_local_ppf(
-                _ptr(xyz), _ptr(normals), self.b, self.n, self.k, int(self.relative),
-                _ptr(idx), _ptr(self.knn_dist), _ptr(ppf_out), _ptr(kws),
-                kws.numel(), stream), "knn_local_ppf")
+        head = (_ptr(xyz), _ptr(normals), self.b, self.n, self.k, int(self.relative))
+        idx, dist, ppf = _ptr(st.knn_idx), _ptr(self.knn_dist), _ptr(self._ppf(slot))
+        tail = (_ptr(st.knn_ws), st.knn_ws.numel(), stream)
+        if not sorted_ok:  # no sorted path: sort + selection + PPF in one call
+            _lib.check(lib.pcr_knn_local_ppf(*head, idx, dist, ppf, *tail), "knn_local_ppf")
             return
-        lib = _lib.load()
-        if self.split_ppf and ppf and self.knn_dist is None and events is not None:
-            # the same two launches with timing events around the selection
+        if dist is not None:
+            # distances wanted: the selection writes in original order, then
+            # the PPF as its own launch (one thread per (slot, point))
+            _lib.check(lib.pcr_knn_local_ppf_prepared(*head, idx, dist, None, *tail),
+                       "knn_local_ppf_prepared")
+            _lib.check(lib.pcr_local_ppf_forward(
+                _ptr(xyz), _ptr(normals), _ptr(xyz), _ptr(normals), idx, self.b, self.n, self.n,
+                self.k, 1, int(self.relative), ppf, stream), "local_ppf_forward")
+            return
+        if events is not None:
+            # pcr_knn_select_ppf's two launches with timing events around the
+            # selection
             ev0, ev1 = events
             ev0.record(torch_stream)
-            rs = lib.pcr_knn_select_sorted(_ptr(xyz), self.b, self.n, self.k, _ptr(kws),
-                                           kws.numel(), stream)
+            rs = lib.pcr_knn_select_sorted(_ptr(xyz), self.b, self.n, self.k, *tail)
             ev1.record(torch_stream)
             if rs == 0:
-                _lib.check(lib.pcr_knn_ppf_sorted(
-                    _ptr(xyz), _ptr(normals), self.b, self.n, self.k, int(self.relative),
-                    _ptr(idx), _ptr(ppf_out), _ptr(kws), kws.numel(), stream),
-                    "knn_ppf_sorted")
+                _lib.check(lib.pcr_knn_ppf_sorted(*head, idx, ppf, *tail), "knn_ppf_sorted")
                 return
             if rs != -3:  # PCR_ERR_UNSUPPORTED: nothing launched
                 _lib.check(rs, "knn_select_sorted")
@@ -175,75 +178,41 @@ class SphExtractor:
             # around the fallback below (its selection + PPF), so they never
             # read ~0 for a launch that ran outside them
             ev0.record(torch_stream)
-        else:
-            events = None
-        if self.split_ppf and ppf and self.knn_dist is None:
-            # selection in sorted query order + the PPF launch that writes
-            # knn_idx and the PPF (pcr_knn_select_ppf)
-            _lib.check(lib.pcr_knn_select_ppf(
-                _ptr(xyz), _ptr(normals), self.b, self.n, self.k, int(self.relative), _ptr(idx),
-                _ptr(ppf_out), _ptr(kws), kws.numel(), stream), "knn_select_ppf")
-            if events is not None:
-                events[1].record(torch_stream)
-            return
-        _lib.check(lib.pcr_knn_local_ppf_prepared(
-            _ptr(xyz), _ptr(normals), self.b, self.n, self.k, int(self.relative),
-            _ptr(idx), _ptr(self.knn_dist), None if self.split_ppf else
-            _ptr(ppf_out), _ptr(kws), kws.numel(), stream), "knn_local_ppf_prepared")
-        if self.split_ppf and ppf:
-            # PPF as its own launch: one thread per (slot, point), coalesced
-            _lib.check(lib.pcr_local_ppf_forward(
-                _ptr(xyz), _ptr(normals), _ptr(xyz), _ptr(normals), _ptr(idx), self.b,
-                self.n, self.n, self.k, 1, int(self.relative), _ptr(ppf_out), stream),
-                "local_ppf_forward")
-
-    def voxel_stage(self, xyz, features, stream, desc=None):
-        """prep + the fused grid / devox / descriptor kernel, one call."""
-        d = self.desc if desc is None else desc
-        _lib.check(_lib.load().pcr_extractor_voxel_stage(
-            _ptr(xyz), _ptr(features), self.b, self.c, self.n, self.r, _ptr(self.norm_coords),
-            _ptr(self.ind), _ptr(self.cnt), _ptr(self.grid), _ptr(self.devox), _ptr(self.dinds),
-            _ptr(self.dwgts), _ptr(d), _ptr(self.ws), self.ws.numel(), stream),
-            "extractor_voxel_stage")
+        # selection in sorted query order + the PPF launch that writes knn_idx
+        # and the PPF, or the two-call path where that does not apply
+        _lib.check(lib.pcr_knn_select_ppf(*head, idx, ppf, *tail), "knn_select_ppf")
+        if events is not None:
+            events[1].record(torch_stream)
 
     def voxel_prep(self, xyz, stream, slot=0):
-        _, ws, dinds, dwgts, _ = self._set(slot)
+        st = self._set(slot)
         nc, ind, _, _ = self._vset(slot)
         _lib.check(_lib.load().pcr_extractor_voxel_prep(
             _ptr(xyz), self.b, self.n, self.r, _ptr(nc), _ptr(ind),
-            _ptr(dinds), _ptr(dwgts), _ptr(ws), ws.numel(), stream), "extractor_voxel_prep")
+            _ptr(st.dinds), _ptr(st.dwgts), _ptr(st.ws), st.ws.numel(), stream),
+            "extractor_voxel_prep")
 
     def voxel_grid(self, features, stream, slot=0):
-        """The dominant kernel (vox_grid_kernel<1>: means -> dense grid + cnt)."""
-        ws = self._set(slot)[1]
+        """Voxel means -> dense grid + cnt (vox_grid_kernel<1>), the eager
+        step's grid launch."""
+        ws = self._set(slot).ws
         _lib.check(_lib.load().pcr_extractor_voxel_grid(
             _ptr(features), self.b, self.c, self.n, self.r, _ptr(self.cnt), _ptr(self.grid),
             _ptr(ws), ws.numel(), stream), "extractor_voxel_grid")
 
-    def voxel_grid_devox(self, features, stream, desc=None, slot=0):
-        """The dominant kernel of the default step (vox_grid_kernel<3>: dense
-        grid + cnt, devox + descriptor from the same LDS means)."""
-        _, ws, dinds, dwgts, _ = self._set(slot)
-        d = self.desc if desc is None else desc
-        _lib.check(_lib.load().pcr_extractor_voxel_grid_devox(
-            _ptr(features), self.b, self.c, self.n, self.r, _ptr(self.cnt), _ptr(self.grid),
-            _ptr(self.devox), _ptr(dinds), _ptr(dwgts), _ptr(d), _ptr(ws),
-            ws.numel(), stream), "extractor_voxel_grid_devox")
-
     def voxel_means_devox(self, features, stream, desc=None, slot=0):
         """Voxel means of the occupied segments into the workspace + devox +
         descriptor (the first half of the split voxel stage)."""
-        _, ws, dinds, dwgts, _ = self._set(slot)
-        _, _, devox, vdesc = self._vset(slot)
-        d = vdesc if desc is None else desc
+        st = self._set(slot)
         _lib.check(_lib.load().pcr_extractor_voxel_means_devox(
-            _ptr(features), self.b, self.c, self.n, self.r, _ptr(devox), _ptr(dinds),
-            _ptr(dwgts), _ptr(d), _ptr(ws), ws.numel(), stream), "extractor_voxel_means_devox")
+            _ptr(features), self.b, self.c, self.n, self.r, _ptr(self._vset(slot)[2]),
+            _ptr(st.dinds), _ptr(st.dwgts), _ptr(self._desc(slot, desc)), _ptr(st.ws),
+            st.ws.numel(), stream), "extractor_voxel_means_devox")
 
     def voxel_means(self, features, stream, slot=0):
         """Voxel means of the occupied segments into the workspace only (the
         devox + descriptor then ride in voxel_stream_devox)."""
-        ws = self._set(slot)[1]
+        ws = self._set(slot).ws
         _lib.check(_lib.load().pcr_extractor_voxel_means(
             _ptr(features), self.b, self.c, self.n, self.r, _ptr(ws), ws.numel(), stream),
             "extractor_voxel_means")
@@ -252,17 +221,16 @@ class SphExtractor:
         """The dense grid + cnt, devox and descriptor from the workspace means
         (pcr_extractor_voxel_stream_devox: each grid workgroup reads the
         cloud's corner data once)."""
-        _, ws, _, dwgts, _ = self._set(slot)
-        _, _, devox, vdesc = self._vset(slot)
-        d = vdesc if desc is None else desc
+        st = self._set(slot)
         _lib.check(_lib.load().pcr_extractor_voxel_stream_devox(
-            self.b, self.c, self.n, self.r, _ptr(self.cnt), _ptr(self.grid), _ptr(devox),
-            _ptr(dwgts), _ptr(d), _ptr(ws), ws.numel(), stream), "extractor_voxel_stream_devox")
+            self.b, self.c, self.n, self.r, _ptr(self.cnt), _ptr(self.grid),
+            _ptr(self._vset(slot)[2]), _ptr(st.dwgts), _ptr(self._desc(slot, desc)), _ptr(st.ws),
+            st.ws.numel(), stream), "extractor_voxel_stream_devox")
 
     def voxel_stream(self, stream, slot=0):
         """The dense grid + cnt from the workspace means (the dominant,
         HBM-bound kernel of the split voxel stage)."""
-        ws = self._set(slot)[1]
+        ws = self._set(slot).ws
         _lib.check(_lib.load().pcr_extractor_voxel_stream(
             self.b, self.c, self.n, self.r, _ptr(self.cnt), _ptr(self.grid), _ptr(ws),
             ws.numel(), stream), "extractor_voxel_stream")
@@ -270,20 +238,20 @@ class SphExtractor:
     def grid_devox(self, stream, desc=None, slot=0):
         """Devox + descriptor from the dense grid (after voxel_grid on the
         same stream): the 80 corner voxels per channel staged in LDS."""
-        _, _, dinds, dwgts, _ = self._set(slot)
-        _, _, devox, vdesc = self._vset(slot)
-        d = vdesc if desc is None else desc
+        st = self._set(slot)
         _lib.check(_lib.load().pcr_extractor_grid_devox(
-            _ptr(self.grid), _ptr(dinds), _ptr(dwgts), self.b, self.c, self.n, self.r,
-            _ptr(devox), _ptr(d), stream), "extractor_grid_devox")
+            _ptr(self.grid), _ptr(st.dinds), _ptr(st.dwgts), self.b, self.c, self.n, self.r,
+            _ptr(self._vset(slot)[2]), _ptr(self._desc(slot, desc)), stream),
+            "extractor_grid_devox")
 
     def voxel_devox(self, features, stream, desc=None, slot=0):
-        _, ws, dinds, dwgts, _ = self._set(slot)
-        _, _, devox, vdesc = self._vset(slot)
-        d = vdesc if desc is None else desc
+        """Devox + descriptor from voxel means re-formed from the features
+        (pcr_extractor_voxel_devox) instead of from the dense grid."""
+        st = self._set(slot)
         _lib.check(_lib.load().pcr_extractor_voxel_devox(
-            _ptr(features), self.b, self.c, self.n, self.r, _ptr(devox), _ptr(dinds),
-            _ptr(dwgts), _ptr(d), _ptr(ws), ws.numel(), stream), "extractor_voxel_devox")
+            _ptr(features), self.b, self.c, self.n, self.r, _ptr(self._vset(slot)[2]),
+            _ptr(st.dinds), _ptr(st.dwgts), _ptr(self._desc(slot, desc)), _ptr(st.ws),
+            st.ws.numel(), stream), "extractor_voxel_devox")
 
     def _check_inputs(self, xyz, normals, features):
         for t, name in ((xyz, "xyz"), (normals, "normals"), (features, "features")):
@@ -540,13 +508,13 @@ class SphExtractor:
             self._vsep = False
 
     def outputs(self, slot=0, idx_slot=0):
-        _, _, dinds, dwgts, _ = self._set(slot)
+        st = self._set(slot)
         nc, ind, devox, desc = self._vset(slot)
         return {
-            "knn_idx": self._set(idx_slot)[4], "local_ppf": self._ppf(idx_slot),
+            "knn_idx": self._set(idx_slot).knn_idx, "local_ppf": self._ppf(idx_slot),
             "norm_coords": nc,
             "ind": ind, "cnt": self.cnt, "grid": self.grid, "devox": devox,
-            "dinds": dinds, "dwgts": dwgts, "desc": desc,
+            "dinds": st.dinds, "dwgts": st.dwgts, "desc": desc,
         }
 
     def _get_runner(self, timed_steps):
@@ -605,11 +573,11 @@ class SphExtractor:
         a.norm_coords, a.ind, a.cnt, a.grid = _ptr(self.norm_coords), _ptr(self.ind), \
             _ptr(self.cnt), _ptr(self.grid)
         a.devox, a.desc = _ptr(self.devox), _ptr(self.desc)
-        a.dinds[0], a.dinds[1] = _ptr(self.dinds), _ptr(s1[2])
-        a.dwgts[0], a.dwgts[1] = _ptr(self.dwgts), _ptr(s1[3])
-        a.knn_ws[0], a.knn_ws[1] = _ptr(self.knn_ws), _ptr(s1[0])
+        a.dinds[0], a.dinds[1] = _ptr(self.dinds), _ptr(s1.dinds)
+        a.dwgts[0], a.dwgts[1] = _ptr(self.dwgts), _ptr(s1.dwgts)
+        a.knn_ws[0], a.knn_ws[1] = _ptr(self.knn_ws), _ptr(s1.knn_ws)
         a.knn_ws_bytes = self.knn_ws.numel()
-        a.vox_ws[0], a.vox_ws[1] = _ptr(self.ws), _ptr(s1[1])
+        a.vox_ws[0], a.vox_ws[1] = _ptr(self.ws), _ptr(s1.ws)
         a.vox_ws_bytes = self.ws.numel()
         if getattr(self, "_ws3", None) is None:
             # the third voxel workspace of runner schedule 7
@@ -639,26 +607,30 @@ class SphExtractor:
         registration.PairMatch whose buffers receive, every step, the
         mutual-NN matching of clouds [0, B/2) against [B/2, B)."""
         self._check_inputs(xyz, normals, features)
-        # timed: True = every step, an int N = N steps in the middle of the run
-        ntimed = min(steps, (steps if timed is True else int(timed)) if timed else 0)
-        runner = self._get_runner(ntimed)
-        if self._runner_cap:
-            _lib.check(_lib.load().pcr_runner_set_timed(runner, ntimed), "runner_set_timed")
         # the argument block is built once per (inputs, match) and reused:
         # every other pointer is an extractor buffer, fixed for its life
         key = (xyz.data_ptr(), normals.data_ptr(), features.data_ptr(), match)
         if self._args_key != key:
             self._args = self._make_args(xyz, normals, features, match)
             self._args_key = key
-        a = self._args
+        self._run(steps, schedule, desc_steps, timed)
+        return self.outputs(slot=0)
+
+    def _run(self, steps, schedule, desc_steps, timed):
+        """pcr_extractor_run over the cached argument block (the tail of
+        run_native and run_ring).  timed: True = every step, an int N = N
+        steps in the middle of the run."""
+        ntimed = min(steps, (steps if timed is True else int(timed)) if timed else 0)
+        runner = self._get_runner(ntimed)
+        if self._runner_cap:
+            _lib.check(_lib.load().pcr_runner_set_timed(runner, ntimed), "runner_set_timed")
         if desc_steps is not None and tuple(desc_steps.shape) != (steps, self.b, self.c):
             raise RuntimeError("desc_steps must be [steps, B, C]")
         cur = torch.cuda.current_stream(self.device)
         _lib.check(_lib.load().pcr_extractor_run(
-            runner, ctypes.byref(a), steps, schedule, _ptr(desc_steps), cur.cuda_stream,
+            runner, ctypes.byref(self._args), steps, schedule, _ptr(desc_steps), cur.cuda_stream,
             self.s_nbr.cuda_stream, self.s_pre.cuda_stream, self.s_vox.cuda_stream),
             "extractor_run")
-        return self.outputs(slot=0)
 
     # ------------------------------------------------------------ batch ring
     def ring_outputs(self, nsets, match_pairs=0):
@@ -714,10 +686,6 @@ class SphExtractor:
             raise RuntimeError("run_ring needs at least one batch")
         mp = match.pairs if match is not None else 0
         ring = self.ring_outputs(R, mp)
-        ntimed = min(steps, (steps if timed is True else int(timed)) if timed else 0)
-        runner = self._get_runner(ntimed)
-        if self._runner_cap:
-            _lib.check(_lib.load().pcr_runner_set_timed(runner, ntimed), "runner_set_timed")
         # the same batch tuples as the last call (tuples are immutable, so
         # the same tensors): checked and keyed then.  Checking 20 batches
         # and keying their pointers cost ~23 us of host time in front of
@@ -744,15 +712,8 @@ class SphExtractor:
                 st.match_count = _ptr(o["count"]) if "count" in o else None
             a.nsets, a.sets = R, sets
             self._args, self._args_key, self._ring_sets = a, key, sets
-        a = self._args
-        a.set0 = int(set0) % R
-        if desc_steps is not None and tuple(desc_steps.shape) != (steps, self.b, self.c):
-            raise RuntimeError("desc_steps must be [steps, B, C]")
-        cur = torch.cuda.current_stream(self.device)
-        _lib.check(_lib.load().pcr_extractor_run(
-            runner, ctypes.byref(a), steps, schedule, _ptr(desc_steps), cur.cuda_stream,
-            self.s_nbr.cuda_stream, self.s_pre.cuda_stream, self.s_vox.cuda_stream),
-            "extractor_run")
+        self._args.set0 = int(set0) % R
+        self._run(steps, schedule, desc_steps, timed)
         return ring
 
     def capture(self, xyz, normals, features):
@@ -779,8 +740,9 @@ class SphExtractor:
 
 
 def grid_kernel_bytes_per_cloud(n, r, c):
-    """Algorithmic HBM bytes of the dominant kernel (vox_grid_kernel<1>: the
-    spherical_avg_voxelize output) per cloud: features read
+    """Algorithmic HBM bytes of the eager step's grid kernel
+    (vox_grid_kernel<1>: the spherical_avg_voxelize output) per
+    cloud: features read
     4CN, grid written 4C r^3, cnt written 4 r^3.  The prep metadata it also
     reads (occupancy bitmap + word prefix r^3/4 bytes, segment offsets and
     point order 8N) is not counted: it is an artefact of this design."""

@@ -26,7 +26,7 @@ def expected_step(xyz, nrm, feat, k, r):
     grid, ind, cnt = oracle.spherical_avg_voxelize_forward(feat, nc, r)
     devox, dinds, dwgts = oracle.spherical_trilinear_devoxelize_forward(r, nc, grid, ind)
     desc = devox.max(axis=2)
-    return dict(knn_idx=ki, local_ppf=lppf, norm_coords=nc, ind=ind, cnt=cnt, grid=grid,
+    return dict(knn_idx=ki, knn_dist=ki_d, local_ppf=lppf, norm_coords=nc, ind=ind, cnt=cnt, grid=grid,
                 devox=devox, dinds=dinds, dwgts=dwgts, desc=desc)
 
 
@@ -107,20 +107,28 @@ def test_extractor_native_runner(dev):
             ex.run_native(tx, tn, tf, 2, schedule=gone)
 
 
-@pytest.mark.parametrize("schedule", [0, 6, 7])
-def test_extractor_runner_batch_ring(dev, schedule):
-    """pcr_extractor_run over a batch ring of 3 distinct batches (each with
-    its own output set): one call of 3 steps, then a call of 5 steps that
-    continues the cycle at set0 = 3 % 3 and wraps (sets 0 and 1 written
-    twice, by batches 0 and 1 again).  After each call every set holds the
-    oracle's outputs of its batch; desc_steps holds every step's
-    descriptor."""
+_ring_exp = {}
+
+
+def _ring_case(b, n, c, k, r):
+    """Three distinct batches of one shape and their oracle outputs, computed
+    once and shared by the cases below (read only)."""
+    key = (b, n, c, k, r)
+    if key not in _ring_exp:
+        batches = [gaussian_clouds(b, n, seed=80 + i, c=c) for i in range(3)]
+        _ring_exp[key] = (batches, [expected_step(*bt, k, r) for bt in batches])
+    return _ring_exp[key]
+
+
+def _check_batch_ring(dev, schedule, shape, stream_devox, with_dist):
     from pcr_amd.extractor import SphExtractor
-    b, n, c, k, r = 4, 1024, 16, 32, 32
-    batches = [gaussian_clouds(b, n, seed=80 + i, c=c) for i in range(3)]
+    b, n, c, k, r = shape
+    batches, exp = _ring_case(*shape)
     tb = [tuple(T(a, dev) for a in bt) for bt in batches]
-    exp = [expected_step(*bt, k, r) for bt in batches]
-    ex = SphExtractor(b, n, c, k, r, device=dev)
+    ex = SphExtractor(b, n, c, k, r, device=dev, stream_devox=stream_devox, with_dist=with_dist)
+    keys = ("knn_idx", "ind", "cnt", "dinds", "dwgts", "norm_coords", "grid", "devox")
+    if with_dist:
+        keys += ("knn_dist",)
     set0 = 0
     for steps in (3, 5):
         ring = ex.ring_outputs(3)
@@ -131,14 +139,36 @@ def test_extractor_runner_batch_ring(dev, schedule):
         ex.run_ring(tb, steps, set0, desc_steps, schedule=schedule)
         torch.cuda.synchronize()
         for i in range(3):
-            for key in ("knn_idx", "ind", "cnt", "dinds", "dwgts", "norm_coords", "grid",
-                        "devox"):
+            for key in keys:
                 assert np.array_equal(N(ring[i][key]), exp[i][key]), (steps, i, key)
             assert np.array_equal(N(ring[i]["local_ppf"]), exp[i]["local_ppf"],
                                   equal_nan=True), (steps, i)
         for s in range(steps):
             assert np.array_equal(N(desc_steps[s]), exp[(set0 + s) % 3]["desc"]), (steps, s)
         set0 = (set0 + steps) % 3
+
+
+@pytest.mark.parametrize("schedule", [0, 6, 7])
+@pytest.mark.parametrize("stream_devox", [True, False])
+@pytest.mark.parametrize("b,n,c,k,r", [(4, 1024, 16, 32, 32), (2, 1500, 5, 16, 16)])
+def test_extractor_runner_batch_ring(dev, schedule, stream_devox, b, n, c, k, r):
+    """pcr_extractor_run over a batch ring of 3 distinct batches (each with
+    its own output set): one call of 3 steps, then a call of 5 steps that
+    continues the cycle at set0 = 3 % 3 and wraps (sets 0 and 1 written
+    twice, by batches 0 and 1 again).  After each call every set holds the
+    oracle's outputs of its batch; desc_steps holds every step's
+    descriptor.  With the devox in the grid stream (where it applies) and in
+    the means launch (devox_in_means); the 1500-point shape takes the
+    1024-thread prep, the 512-thread means, the 17-piece grid stream (means
+    + devox, then stream, under schedules 6 / 7) and the 2048-candidate
+    selection."""
+    _check_batch_ring(dev, schedule, (b, n, c, k, r), stream_devox, False)
+
+
+def test_extractor_runner_batch_ring_knn_dist(dev):
+    """The runner's selection with distances wanted (knn_dist in every ring
+    set): distances, ids and everything else equal to the oracle."""
+    _check_batch_ring(dev, 6, (4, 1024, 16, 32, 32), True, True)
 
 
 def test_extractor_runner_ring_list_mutated(dev):
@@ -260,6 +290,77 @@ def test_voxel_back_half_variants_identical(dev, b, n, c, r, with_desc):
         assert np.array_equal(N(devox), ref["devox"])
         if with_desc:
             assert np.array_equal(N(desc), ref["desc"])
+
+
+_entry_exp = {}
+
+
+@pytest.mark.parametrize("path,n,r", [("stage", 200, 8), ("stage", 700, 8), ("stage", 1500, 8),
+                                      ("grid_devox", 700, 8), ("grid+grid_devox", 700, 8),
+                                      ("grid+voxel_devox", 700, 8), ("means_devox", 2049, 16)])
+def test_voxel_entry_points_match_oracle(dev, path, n, r):
+    """The exported voxel entry points no extractor path composes, called
+    directly and compared with the oracle: the one-call stage at the three
+    prep thread counts (<= 256, <= 1024, more points), the three ways to the
+    grid + devox + descriptor after one prep, and means_devox one point past
+    its own kernel's limit (the grid-kernel fallback).  Three channels: the
+    last channel group holds one."""
+    from pcr_amd import _lib
+    from pcr_amd.ops import _ptr
+    lib = _lib.load()
+    b, c = 2, 3
+    xyz, nrm, feat = gaussian_clouds(b, n, seed=3 * n + r, c=c)
+    if (n, r) not in _entry_exp:
+        _entry_exp[(n, r)] = expected_step(xyz, nrm, feat, 1, r)
+    exp = _entry_exp[(n, r)]
+    tx, tf = T(xyz, dev), T(feat, dev)
+    r3 = r ** 3
+    ws = torch.full((lib.pcr_extractor_workspace_size(b, n, c, r),), 0xA5, dtype=torch.uint8,
+                    device=dev)
+    i32, f32 = dict(dtype=torch.int32, device=dev), dict(device=dev)
+    out = dict(norm_coords=torch.full((b, 3, n), float("nan"), **f32),
+               ind=torch.full((b, n), -7, **i32), cnt=torch.full((b, r3), -7, **i32),
+               grid=torch.full((b, c, r3), float("nan"), **f32),
+               devox=torch.full((b, c, n), float("nan"), **f32),
+               dinds=torch.full((b, 8, n), -7, **i32),
+               dwgts=torch.full((b, 8, n), float("nan"), **f32),
+               desc=torch.full((b, c), float("nan"), **f32))
+    o = {kk: _ptr(v) for kk, v in out.items()}
+    st = torch.cuda.current_stream().cuda_stream
+    wsp, wsn = _ptr(ws), ws.numel()
+    keys = ("grid", "cnt", "devox", "desc")
+    if path == "stage":
+        _lib.check(lib.pcr_extractor_voxel_stage(
+            _ptr(tx), _ptr(tf), b, c, n, r, o["norm_coords"], o["ind"], o["cnt"], o["grid"],
+            o["devox"], o["dinds"], o["dwgts"], o["desc"], wsp, wsn, st), "stage")
+        keys = tuple(out)
+    else:
+        _lib.check(lib.pcr_extractor_voxel_prep(
+            _ptr(tx), b, n, r, o["norm_coords"], o["ind"], o["dinds"], o["dwgts"], wsp, wsn, st),
+            "prep")
+    if path == "grid_devox":
+        _lib.check(lib.pcr_extractor_voxel_grid_devox(
+            _ptr(tf), b, c, n, r, o["cnt"], o["grid"], o["devox"], o["dinds"], o["dwgts"],
+            o["desc"], wsp, wsn, st), "grid_devox")
+    elif path.startswith("grid+"):
+        _lib.check(lib.pcr_extractor_voxel_grid(_ptr(tf), b, c, n, r, o["cnt"], o["grid"], wsp,
+                                                wsn, st), "grid")
+        if path == "grid+grid_devox":
+            _lib.check(lib.pcr_extractor_grid_devox(
+                o["grid"], o["dinds"], o["dwgts"], b, c, n, r, o["devox"], o["desc"], st),
+                "grid_devox")
+        else:
+            _lib.check(lib.pcr_extractor_voxel_devox(
+                _ptr(tf), b, c, n, r, o["devox"], o["dinds"], o["dwgts"], o["desc"], wsp, wsn,
+                st), "voxel_devox")
+    elif path == "means_devox":
+        _lib.check(lib.pcr_extractor_voxel_means_devox(
+            _ptr(tf), b, c, n, r, o["devox"], o["dinds"], o["dwgts"], o["desc"], wsp, wsn, st),
+            "means_devox")
+        keys = ("devox", "desc")
+    torch.cuda.synchronize()
+    for key in keys:
+        assert np.array_equal(N(out[key]), exp[key]), key
 
 
 def test_extractor_full_size_properties(dev):

@@ -41,6 +41,8 @@ def check_sorted(dev, xyz, nrm, k, exp_idx):
     bad = np.argwhere(got != exp_idx)
     assert bad.size == 0, "sorted-path idx differs at %d places, first %s: got %s exp %s" % (
         len(bad), bad[:3].tolist(), got[tuple(bad[0])], exp_idx[tuple(bad[0])])
+    ep = oracle.local_ppf(xyz, nrm, xyz, nrm, exp_idx, kmajor=True, relative=True)
+    assert np.array_equal(N(ppf), ep, equal_nan=True)
 
 
 def check_self(dev, xyz, k):
@@ -151,6 +153,22 @@ def test_select_sorted_2k_edge_cases(dev, n):
     for k in (32, 16, 1):
         _, ei = oracle.knn_dir(xyz, xyz, k)
         check_sorted(dev, xyz, nrm, k, ei)
+
+
+@pytest.mark.parametrize("b,n,k,kind", [(33, 1024, 32, "gauss"), (130, 300, 16, "gauss"),
+                                        (33, 1024, 32, "edge")])
+def test_select_sorted_narrow_chunks(dev, b, n, k, kind):
+    """The selection's chunk width drops from 12 to 8 slots per wave once
+    ceil(n / 64) * b * 8 > 4096 workgroups (knn_wsel_kernel<16, 8>, what every
+    c4 rank runs): the smallest batches past that line, 16 * 33 = 528 and
+    5 * 130 = 650 blocks (> 512), and the tie-heavy lattice at the first."""
+    if kind == "edge":
+        xyz = np.ascontiguousarray(np.concatenate(
+            [edge_clouds_for_knn(3, n, seed=5 + i) for i in range(11)]))
+    else:
+        xyz, _, _ = gaussian_clouds(b, n, seed=b + n)
+    nrm = np.ascontiguousarray(np.roll(xyz, 1, axis=1))
+    check_sorted(dev, xyz, nrm, k, oracle.knn_forward(xyz, xyz, k)[2])
 
 
 def test_select_two_sets(dev):
