@@ -345,6 +345,35 @@ pcr_status pcr_mutual_nn_match_cm(const float *f1, const float *f2, int p, int n
                                   int *corr12, int *corr21, int *idx1, int *idx2, int *count,
                                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------- rigid transform from the correspondences -------
+ * The step after the matching (datasets/deepgmr_mn40.py:165-231
+ * register_one_pair, there Open3D RANSAC on the CPU), for p pairs: a seeded,
+ * deterministic RANSAC and a least-squares refit (the scalar
+ * math is include/pcr_rigid.h).
+ *   xyz1 [p,3,n1], xyz2 [p,3,n2]; idx1 / idx2 [p,n1] and count [p] as the
+ *   matching emits them: slot s < count[q] pairs xyz1[q,:,idx1[q,s]] with
+ *   xyz2[q,:,idx2[q,s]].
+ *   Hypothesis h of pair q takes the three distinct slots its integer sampler
+ *   draws from (seed, q, h, count[q]); it is rejected (score -1) by the edge-length check
+ *   (edge_ratio in [0, 1), 0: only zero-length edges reject), else solved in
+ *   fp64 (b ~ R a + t, det R = +1) and scored by the number of slots whose
+ *   fp32 residual is <= inlier_dist.  The best score wins, ties to the lowest
+ *   h; refine_iters times: mask under the current transform, least squares
+ *   over the mask (stops when fewer than 3 slots remain).
+ *   transform [p,4,4] fp64 row-major; inliers [p,n1] 0/1 per slot and
+ *   num_inliers [p] under the final transform; best_hyp [p] (-1: none);
+ *   scores [p,hyps] (NULL: not wanted); status [p]: 0 ok, 1 count < 3,
+ *   2 every hypothesis rejected (1 / 2: identity, no inliers).
+ * Bit-identical from run to run.  Runs on `stream`; the workspace is the
+ * caller's. */
+size_t pcr_rigid_ransac_workspace_size(int p, int n1, int hyps);
+pcr_status pcr_rigid_ransac(const float *xyz1, const float *xyz2, int p, int n1, int n2,
+                            const int *idx1, const int *idx2, const int *count,
+                            int hyps, float inlier_dist, float edge_ratio, int refine_iters,
+                            unsigned seed, double *transform, int *inliers, int *num_inliers,
+                            int *best_hyp, int *scores, int *status,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------ LRF change_coords (8f f2) ----------
  * models/pvcnn_classify.py:153-184 (rot_invariant_preprocess ==
  * 'change_coords'), one cloud per workgroup, no host round trip.

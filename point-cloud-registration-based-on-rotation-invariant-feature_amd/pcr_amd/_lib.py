@@ -73,6 +73,9 @@ SIGNATURES = {
     "pcr_mutual_nn_workspace_size": (SZ, [I, I, I]),
     "pcr_mutual_nn_match": (ST, [P, P, I, I, I, I, P, P, P, P, P, P, SZ, P]),
     "pcr_mutual_nn_match_cm": (ST, [P, P, I, I, I, I, P, P, P, P, P, P, SZ, P]),
+    "pcr_rigid_ransac_workspace_size": (SZ, [I, I, I]),
+    "pcr_rigid_ransac": (ST, [P, P, I, I, I, P, P, P, I, F, F, I, ctypes.c_uint, P, P, P, P, P, P,
+                             P, SZ, P]),
     "pcr_lrf_change_coords": (ST, [P, I, I, P, P, P, P, P]),
     "pcr_gather_features_forward": (ST, [P, P, I, I, I, I, P, P]),
     "pcr_gather_features_backward": (ST, [P, P, I, I, I, I, P, P]),

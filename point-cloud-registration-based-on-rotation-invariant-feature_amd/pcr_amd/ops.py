@@ -517,3 +517,46 @@ def find_correspondence_one_pair(feat1, feat2):
     _, _, idx1, idx2, count = mutual_nn_match(feat1.unsqueeze(0), feat2.unsqueeze(0))
     n = int(count[0].item())
     return idx1[0, :n].long(), idx2[0, :n].long()
+
+
+def rigid_ransac(xyz1, xyz2, idx1, idx2, count, hyps=1000, inlier_dist=0.08, edge_ratio=0.9,
+                 refine_iters=2, seed=0, return_scores=False, workspace=None):
+    """Rigid transforms of p registration pairs from their correspondences
+    (datasets/deepgmr_mn40.py:165-231 register_one_pair(func='ransac'),
+    batched; the defaults follow its max_iter=1000, voxel_size=0.08 and edge
+    length 0.9): xyz1 [p, 3, n1], xyz2 [p, 3, n2], idx1 / idx2 [p, n1] and
+    count [p] as mutual_nn_match returns them -> (transform [p, 4, 4] fp64
+    with xyz2 ~ R xyz1 + t, inliers [p, n1] 0/1 per correspondence slot,
+    num_inliers [p], best_hyp [p], status [p]: 0 ok, 1 fewer than 3
+    correspondences, 2 every hypothesis rejected), plus scores [p, hyps] with
+    return_scores.  Seeded and bit-identical from run to run."""
+    _check(xyz1, "xyz1")
+    _check(xyz2, "xyz2")
+    _check(idx1, "idx1", "int")
+    _check(idx2, "idx2", "int")
+    _check(count, "count", "int")
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
+            xyz1.shape[0] != xyz2.shape[0]:
+        raise RuntimeError("rigid_ransac: expected [p, 3, n] clouds with equal pair counts")
+    p, _, n1 = xyz1.shape
+    n2 = xyz2.shape[2]
+    if tuple(idx1.shape) != (p, n1) or tuple(idx2.shape) != (p, n1) or tuple(count.shape) != (p,):
+        raise RuntimeError("rigid_ransac: expected idx1 / idx2 [p, n1] and count [p]")
+    hyps, refine_iters = int(hyps), int(refine_iters)
+    dev = xyz1.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    transform = torch.empty((p, 4, 4), dtype=torch.float64, device=dev)
+    inliers = torch.empty((p, n1), **i32)
+    num_inliers, best_hyp, status = (torch.empty((p,), **i32) for _ in range(3))
+    scores = torch.empty((p, max(hyps, 0)), **i32) if return_scores else None
+    lib = _lib.load()
+    need = max(256, lib.pcr_rigid_ransac_workspace_size(p, n1, hyps))
+    ws = workspace if workspace is not None and workspace.numel() >= need else \
+        torch.empty(need, dtype=torch.uint8, device=dev)
+    _lib.check(lib.pcr_rigid_ransac(
+        _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(idx1), _ptr(idx2), _ptr(count), hyps,
+        float(inlier_dist), float(edge_ratio), refine_iters, int(seed) & 0xFFFFFFFF,
+        _ptr(transform), _ptr(inliers), _ptr(num_inliers), _ptr(best_hyp), _ptr(scores),
+        _ptr(status), _ptr(ws), ws.numel(), _stream()), "rigid_ransac")
+    out = (transform, inliers, num_inliers, best_hyp, status)
+    return out + (scores,) if return_scores else out

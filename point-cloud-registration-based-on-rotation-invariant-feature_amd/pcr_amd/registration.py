@@ -16,6 +16,11 @@ one step of a rank's shard of P pairs is:
     (pcr_amd.distributed.gather_descriptors, RCCL over xGMI) -- the only
     collective.
 
+The correspondences become a rigid transform per pair on the device too
+(ops.rigid_ransac: a seeded RANSAC + least-squares refit):
+PairExtractor.register, or register_pairs for features from elsewhere;
+rre_rte are the reference's error meters.
+
 The native runner (pcr_extractor_run with match_pairs = P) enqueues the
 matching on each step's voxel queue right after its devox (behind the grid
 stream, which evaluates the devox at c2-sized clouds), so S steps of
@@ -97,3 +102,50 @@ class PairExtractor:
 
     def reserve_timing(self, timed_steps):
         self.ex.reserve_timing(timed_steps)
+
+    def register(self, xyz, normals, features, **ransac):
+        """forward, then the rigid transform of every pair from its
+        correspondences (ops.rigid_ransac on the current stream; `ransac`:
+        its keyword arguments): forward's keys plus transform [P, 4, 4] fp64
+        (target ~ R source + t), inliers, num_inliers, best_hyp and
+        reg_status."""
+        out = self.forward(xyz, normals, features)
+        p = self.pairs
+        got = ops.rigid_ransac(xyz[:p], xyz[p:], out["idx1"], out["idx2"], out["count"], **ransac)
+        out.update(zip(("transform", "inliers", "num_inliers", "best_hyp", "reg_status"), got))
+        return out
+
+
+def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, **ransac):
+    """Pair in, transform out (datasets/deepgmr_mn40.py:165-244,
+    find_correspondence_one_pair + register_one_pair(func='ransac'), batched
+    and on the device): xyz1 [p, 3, n1], xyz2 [p, 3, n2] and per-point
+    features [p, n, c] (channel_major: [p, c, n]) -> a dict with the matching
+    (idx1, idx2, count) and ops.rigid_ransac's outputs (transform, inliers,
+    num_inliers, best_hyp, reg_status; scores with return_scores).  The
+    correspondence count never visits the host."""
+    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
+    got = ops.rigid_ransac(xyz1, xyz2, idx1, idx2, count, **ransac)
+    out = {"idx1": idx1, "idx2": idx2, "count": count}
+    out.update(zip(("transform", "inliers", "num_inliers", "best_hyp", "reg_status", "scores"),
+                   got))
+    return out
+
+
+def apply_transform(xyz, transform):
+    """R xyz + t of [p, 3, n] clouds under [p, 4, 4] transforms (the
+    reference's apply_transform(pt1, est)), in the transforms' dtype."""
+    x = xyz.to(transform.dtype)
+    return transform[:, :3, :3] @ x + transform[:, :3, 3:4]
+
+
+def rre_rte(gt, est):
+    """RE_TE_one_pair (datasets/deepgmr_mn40.py:152-164), batched over
+    [p, 4, 4] transforms: the rotation error in degrees,
+    acos(clamp((tr(Rgt^T Rest) - 1) / 2, -1, 1)), and the norm of the
+    translation difference."""
+    gt, est = gt.to(torch.float64), est.to(torch.float64)
+    tr = (gt[:, :3, :3] * est[:, :3, :3]).sum(dim=(1, 2))
+    rre = torch.rad2deg(torch.acos(torch.clamp((tr - 1.0) / 2.0, -1.0, 1.0)))
+    rte = torch.linalg.norm(gt[:, :3, 3] - est[:, :3, 3], dim=1)
+    return rre, rte
