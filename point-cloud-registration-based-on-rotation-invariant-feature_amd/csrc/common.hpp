@@ -45,45 +45,13 @@ inline void allow_big_lds(K kernel, size_t bytes) {
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// knn_spatial.hip: Morton-sorted exact KNN of xyz1 [b,3,n] in xyz2 [b,3,m]
-// (self: the same set).  Returns PCR_ERR_UNSUPPORTED without launching
-// anything when it does not apply.
-enum KnnStage : int {
-  kKnnSort = 1,        // sort the point sets into the workspace
-  kKnnSelect = 2,      // select from an already sorted workspace
-  kKnnSortedRows = 4,  // with kKnnSelect: the selection only writes its neighbour
-                       // ids in sorted query order into the workspace (self,
-                       // k <= 32, clouds of <= 2048 points, idx1 alone)
-};
-// Its optional outputs and PPF inputs; anything may stay null.
-struct KnnIO {
-  float* dist1 = nullptr;  // [b,k,n] xyz1's neighbours in xyz2
-  int* idx1 = nullptr;
-  float* dist2 = nullptr;  // [b,k,m] the other direction, run when idx2 is set
-  int* idx2 = nullptr;
-  // fused local PPF of direction 1 into ppf1 [b,4,k,n]: both sets' normals
-  const float *nrm1 = nullptr, *nrm2 = nullptr;
-  int relative = 0;
-  float* ppf1 = nullptr;
-};
-pcr_status knn_spatial(const float* xyz1, const float* xyz2, int b, int n, int m, int k,
-                       const KnnIO& io, void* ws, size_t ws_bytes, bool self, hipStream_t st,
-                       int stages = kKnnSort | kKnnSelect);
-// views of kKnnSortedRows' output and of the sort's inverse permutation
-constexpr int kKnnSortedK = 32;
-bool knn_sorted_views(void* ws, int b, int n, const int** sidx, const int** inv, int* npad);
-
-// neighbors.hip: selection + local PPF of a prepared (sorted) workspace, the
-// one ladder behind pcr_knn_select_ppf and the runner.  Without dist: the
-// selection writes its neighbour ids in sorted query order -- whole rows --
-// and the PPF kernel reads them back through the sort's inverse permutation
-// while it writes knn_idx [b,k,n] (original order) and the PPF [b,4,k,n].
-// With dist, or on shapes outside that path (k > 32, clouds of more than 2048
-// points, no sorted views): pcr_knn_local_ppf_prepared (selection only) +
-// pcr_local_ppf_forward, same outputs.
-pcr_status knn_select_ppf_prepared(const float* xyz, const float* normals, int b, int n, int k,
-                                   int relative, int* idx, float* dist, float* ppf,
-                                   const void* workspace, size_t workspace_bytes, void* stream);
+// workspace layouts (256-byte aligned regions) and power-of-two sort sizes
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline int next_pow2(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
 
 // Calls f(std::integral_constant<int, KM>) with the smallest KM of 16, 32,
 // 64, 128 that holds k neighbours; false (f not called) when k > 128.
@@ -120,15 +88,6 @@ static __device__ unsigned long long pcr_diag_stamps[1024][16];  // one copy per
 #define PCR_STAMP(p) \
   do {               \
   } while (0)
-#endif
-
-// Experiment knobs (launch shapes, schedule variants) are read from the
-// environment only in the diagnostic build; the product library compiles the
-// default in, so no environment variable can change what a timed run does.
-#ifdef PCR_DIAG
-#define PCR_KNOB(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#else
-#define PCR_KNOB(name, dflt) (dflt)
 #endif
 
 // Issue priority of the latency-bound per-cloud kernels (prep, Morton sort):

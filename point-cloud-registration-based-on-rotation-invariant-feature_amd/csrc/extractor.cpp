@@ -1,14 +1,14 @@
 // extractor.cpp -- native multi-step runner of the sph-dg extractor forward
 // (the bench's pipelined step, include/pcr_amd.h pcr_extractor_run).  Host
-// code only: it enqueues the kernels of voxelize.hip / knn_spatial.hip /
-// neighbors.hip through their C entry points and chains the streams with HIP
+// code only: it enqueues the kernels of voxelize.hip / knn.hip /
+// local_ppf.hip through their C entry points and chains the streams with HIP
 // events, so a Python caller pays one call per S steps instead of a dozen
 // ctypes / torch.cuda.Event operations per step.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
-#include "common.hpp"
+#include "knn_spatial.hpp"
 
 // the KNN chains of a call's first kS6Head steps wait for step 0's voxel
 // means: 20-step calls 366k -> 375k clouds/s (3 interleaved rounds,

@@ -78,6 +78,16 @@ def test_select_ragged_sizes(dev, n):
     check_self(dev, xyz, 32)
 
 
+@pytest.mark.parametrize("n,k", [(700, 48), (700, 100), (1100, 48), (2100, 48)])
+def test_select_k_above_32(dev, n, k):
+    """The cells of the selection's ladder past k = 32, at the smallest shapes
+    that reach them: clouds of <= 1024 points take knn_block_kernel<64> (k =
+    48) and <128> (k = 100), with and without the fused PPF; larger clouds the
+    112-key selection, in original order with the fused PPF up to 2048 points
+    (n = 1100) and as sorted keys + knn_emit_kernel beyond (n = 2100)."""
+    check_self(dev, gaussian_clouds(2, n, seed=n + k)[0], k)
+
+
 def test_select_cached_2k_duplicates_and_k16(dev):
     xyz, _, _ = gaussian_clouds(2, 2048, seed=77)
     xyz[0, :, 500:700] = xyz[0, :, 500:501]  # fallback blocks past the LDS cache
