@@ -374,6 +374,35 @@ pcr_status pcr_rigid_ransac(const float *xyz1, const float *xyz2, int p, int n1,
                             int *best_hyp, int *scores, int *status,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------ point-to-point ICP ------------------
+ * utils/open3d_func.py:63-72 (register_one_pair with func='icp': Open3D
+ * registration_icp, point to point), for p pairs, as a solver of its own or as
+ * the refinement of pcr_rigid_ransac's transform (the scalar
+ * math is include/pcr_rigid.h and pcr_sumsq3f of include/pcr_math.h).
+ *   xyz1 [p,3,n1] source, xyz2 [p,3,n2] target; init [p,4,4] fp64 row-major
+ *   (the upper 3 x 4 is used as it is; NULL: the identity).
+ *   Evaluate(T): T rounded to fp32; every source point moved by the fp32 fmaf
+ *   chain of the residual; its nearest target by the fp32 squared distance
+ *   (lowest index on ties, a non-finite distance never wins) is its
+ *   correspondence when that distance is <= max_dist * max_dist (an fp32
+ *   product), else -1.  M = their number, fitness = M / n1, rmse =
+ *   sqrt(sum of the squared distances / M) in fp64 (0 when M = 0).
+ *   Iterate from Evaluate(init), at most max_iters times: stop with status 1
+ *   when M < 3; T = the fp64 least-squares R, t of the original source points
+ *   onto their correspondences; Evaluate(T); stop with status 0 when
+ *   |fitness change| < rel_fitness and |rmse change| < rel_rmse.  Status 2:
+ *   the iteration limit (max_iters = 0: a pure evaluation of init).
+ *   transform [p,4,4] fp64 (bottom row 0 0 0 1); corr [p,n1], num_corr [p],
+ *   fitness [p], rmse [p]: Evaluate at the reported transform; iterations [p]:
+ *   solves made; status [p].  0 <= max_iters <= 100000; max_dist > 0; the
+ *   tolerances >= 0.  A bad pair (far apart, NaN) never fails the call.
+ * Bit-identical from run to run.  Runs on `stream`; needs no workspace. */
+pcr_status pcr_icp_point_to_point(const float *xyz1, const float *xyz2, int p, int n1, int n2,
+                                  const double *init, float max_dist, int max_iters,
+                                  double rel_fitness, double rel_rmse, double *transform,
+                                  int *corr, int *num_corr, double *fitness, double *rmse,
+                                  int *iterations, int *status, void *stream);
+
 /* ------------------------------------ LRF change_coords (8f f2) ----------
  * models/pvcnn_classify.py:153-184 (rot_invariant_preprocess ==
  * 'change_coords'), one cloud per workgroup, no host round trip.

@@ -14,7 +14,8 @@
  *             method (largest eigenvector of a symmetric 4 x 4 by cyclic
  *             Jacobi sweeps): det R = +1 by construction, no NaN on
  *             degenerate input; pcr_rigid_solve3 feeds it three pairs
- *   score     pcr_rigid_resid2: the fp32 fmaf chain of one residual
+ *   score     pcr_rigid_apply: the fp32 fmaf chain that moves a point;
+ *             pcr_rigid_resid2: the squared residual of one slot under it
  */
 #ifndef PCR_RIGID_H
 #define PCR_RIGID_H
@@ -230,15 +231,26 @@ PCR_HD void pcr_rigid_round(const double *R, const double *t, float *T) {
 }
 
 /* ---- score ---- */
+/* coordinate r of the point a moved by T (pcr_rigid_round): one fp32 fmaf chain */
+PCR_HD float pcr_rigid_apply1(const float *T, int r, float ax, float ay, float az) {
+  return __builtin_fmaf(T[3 * r], ax,
+                        __builtin_fmaf(T[3 * r + 1], ay, __builtin_fmaf(T[3 * r + 2], az, T[9 + r])));
+}
+
+/* the moved point: what the residual subtracts the target from, and what the
+ * ICP (csrc/icp.hip) searches the target cloud with */
+PCR_HD void pcr_rigid_apply(const float *T, float ax, float ay, float az, float *out) {
+  out[0] = pcr_rigid_apply1(T, 0, ax, ay, az);
+  out[1] = pcr_rigid_apply1(T, 1, ax, ay, az);
+  out[2] = pcr_rigid_apply1(T, 2, ax, ay, az);
+}
+
 /* squared residual of one slot under T (pcr_rigid_round); inlier: <= tau * tau */
 PCR_HD float pcr_rigid_resid2(const float *T, float ax, float ay, float az, float bx, float by,
                               float bz) {
-  const float dx =
-      __builtin_fmaf(T[0], ax, __builtin_fmaf(T[1], ay, __builtin_fmaf(T[2], az, T[9]))) - bx;
-  const float dy =
-      __builtin_fmaf(T[3], ax, __builtin_fmaf(T[4], ay, __builtin_fmaf(T[5], az, T[10]))) - by;
-  const float dz =
-      __builtin_fmaf(T[6], ax, __builtin_fmaf(T[7], ay, __builtin_fmaf(T[8], az, T[11]))) - bz;
+  const float dx = pcr_rigid_apply1(T, 0, ax, ay, az) - bx;
+  const float dy = pcr_rigid_apply1(T, 1, ax, ay, az) - by;
+  const float dz = pcr_rigid_apply1(T, 2, ax, ay, az) - bz;
   return dx * dx + dy * dy + dz * dz;
 }
 

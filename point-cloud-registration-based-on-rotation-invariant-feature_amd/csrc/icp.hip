@@ -1,0 +1,339 @@
+// icp.hip -- batched point-to-point ICP for gfx950: the reference's
+// register_one_pair(func='icp') (utils/open3d_func.py:63-72, Open3D
+// registration_icp on the CPU, one pair at a time), as a solver of its own or
+// as the refinement of pcr_rigid_ransac's transform.  The contract is
+// DESIGN.md 4.8b, the scalar math include/pcr_rigid.h + pcr_sumsq3f.
+//
+//   icp_kernel  one workgroup per pair runs the whole iteration loop (bounded
+//     by the uniform max_iters, no host round trip).  The target cloud lies in
+//     LDS as three planes x / y / z padded with NaN to a multiple of kIPad; it
+//     is staged once when it fits one chunk of kIChunk points and re-staged
+//     chunk by chunk otherwise.  A thread owns kIP source points per tile of
+//     kIT * kIP (point i = tile + k * kIT + tid): it moves them by the current
+//     transform and scans the chunk kIPad targets at a time -- their
+//     ds_read_b128 (four targets of one plane, the same address in every lane:
+//     a broadcast) all issued before the first is scored, then independent
+//     distance chains, strict `<` in ascending j, so the lowest index wins a
+//     tie and a NaN never wins.  M, E, the centroid sums
+//     and the centred cross-covariance are per-thread fp64 sums in ascending
+//     point order, a fixed shuffle butterfly, the waves in order (the scheme
+//     of rigid_refit_kernel): no float atomics, the same bits every run.
+//     Wave 0 solves (pcr_rigid_from_cov) and hands R, t to the others through
+//     LDS.  kResident (n1 <= one tile): the source points, their nearest
+//     target and its coordinates stay in registers between the evaluation
+//     and the covariance pass, and corr is written once at the end; larger
+//     n1 keeps the nearest index in corr and re-reads the points.
+#include "common.hpp"
+#include "pcr_rigid.h"
+
+// launch shape; other shapes for A/B builds (make ab DEFS=-DPCR_ICP_THREADS=256
+// -DPCR_ICP_PPT=4)
+#ifndef PCR_ICP_THREADS
+#define PCR_ICP_THREADS 512
+#endif
+#ifndef PCR_ICP_PPT
+#define PCR_ICP_PPT 2
+#endif
+
+namespace pcr {
+
+constexpr int kIT = PCR_ICP_THREADS;  // threads per workgroup
+constexpr int kIP = PCR_ICP_PPT;      // source points per thread and tile
+constexpr int kIW = kIT / kWave;
+constexpr int kITile = kIT * kIP;
+constexpr int kIChunk = 8192;         // target points per LDS chunk (12 bytes each: 96 KB)
+constexpr int kIPad = 16;             // targets per scan step; the planes are NaN-padded to it
+constexpr int kIcpMaxIters = 100000;  // the cap on max_iters
+static_assert(kIT % kWave == 0 && kIT <= 1024 && kIChunk % kIPad == 0, "icp launch shape");
+
+inline int icp_cap(int n2) { return min((n2 + kIPad - 1) / kIPad * kIPad, kIChunk); }
+inline size_t icp_lds_bytes(int cap) {
+  return (size_t)cap * 12 + (size_t)kIW * 16 * sizeof(double) + 16 * sizeof(double);
+}
+
+// Sum of v[0..N) over the workgroup, the same bits in every thread
+// (rigid_block_sum for kIW waves).
+template <int N>
+__device__ inline void icp_block_sum(double (&v)[N], double (*red_s)[16]) {
+  static_assert(N <= 16, "row of red_s");
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < N; i++) v[i] = wave_sum_d(v[i]);
+  if ((tid & (kWave - 1)) == 0) {
+#pragma unroll
+    for (int i = 0; i < N; i++) red_s[tid >> 6][i] = v[i];
+  }
+  lds_barrier();
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    double s = red_s[0][i];
+    for (int w = 1; w < kIW; w++) s += red_s[w][i];
+    v[i] = s;
+  }
+  lds_barrier();
+}
+
+// targets [c0, c0 + len) of the pair -> the three LDS planes, NaN up to the
+// next multiple of kIPad (len <= cap, cap % kIPad == 0)
+__device__ inline void icp_stage(float* tg, int cap, const float* __restrict__ B, int n2, int c0,
+                                 int len) {
+  const int lenp = (len + kIPad - 1) & ~(kIPad - 1);
+  for (int j = threadIdx.x; j < lenp; j += kIT) {
+#pragma unroll
+    for (int d = 0; d < 3; d++)
+      tg[d * cap + j] = j < len ? B[(size_t)d * n2 + c0 + j] : __builtin_nanf("");
+  }
+}
+
+// nearest of the staged targets to each of the thread's moved points
+__device__ inline void icp_scan(const float* tg, int cap, int c0, int len,
+                                const float (&m)[kIP][3], float (&bd)[kIP], int (&bj)[kIP]) {
+  const int lenp = (len + kIPad - 1) & ~(kIPad - 1);
+  for (int j0 = 0; j0 < lenp; j0 += kIPad) {
+    // kIPad / 4 groups of three reads in flight before the first is scored
+#pragma unroll
+    for (int g = 0; g < kIPad / 4; g++) {
+      const int j = j0 + 4 * g;
+      const float4 x = *(const float4*)(tg + j);
+      const float4 y = *(const float4*)(tg + cap + j);
+      const float4 z = *(const float4*)(tg + 2 * cap + j);
+      const float xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w},
+                  zs[4] = {z.x, z.y, z.z, z.w};
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+#pragma unroll
+        for (int k = 0; k < kIP; k++) {
+          const float d = pcr_sumsq3f(m[k][0] - xs[u], m[k][1] - ys[u], m[k][2] - zs[u]);
+          if (d < bd[k]) {
+            bd[k] = d;
+            bj[k] = c0 + j + u;
+          }
+        }
+      }
+    }
+  }
+}
+
+template <bool kResident>
+__global__ __launch_bounds__(kIT) void icp_kernel(
+    const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n1, int n2,
+    const double* __restrict__ init, float tau2, int max_iters, double rel_fitness,
+    double rel_rmse, int cap, double* __restrict__ transform, int* __restrict__ corr,
+    int* __restrict__ num_corr, double* __restrict__ fitness, double* __restrict__ rmse,
+    int* __restrict__ iterations, int* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) char icp_smem[];
+  float* tg = (float*)icp_smem;  // [3][cap]
+  double(*red_s)[16] = (double(*)[16])(icp_smem + (size_t)cap * 12);
+  double* sol_s = (double*)(red_s + kIW);  // R[9], t[3]
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const float* A = xyz1 + (size_t)q * 3 * n1;
+  const float* B = xyz2 + (size_t)q * 3 * n2;
+  int* cq = corr + (size_t)q * n1;
+  const bool whole = n2 <= cap;  // the target stays in LDS
+  const int tiles = kResident ? 1 : (n1 + kITile - 1) / kITile;
+
+  double R[9], t[3];
+  float T[12];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+      R[3 * i + j] = init ? init[(size_t)q * 16 + 4 * i + j] : (i == j ? 1.0 : 0.0);
+    t[i] = init ? init[(size_t)q * 16 + 4 * i + 3] : 0.0;
+  }
+  pcr_rigid_round(R, t, T);
+  if (whole) {
+    icp_stage(tg, cap, B, n2, 0, n2);
+    lds_barrier();
+  }
+
+  // kResident: the tile's points, their nearest target and its coordinates
+  float a[kIP][3], b[kIP][3];
+  int bj[kIP];
+  double M = 0.0, E = 0.0, pfit = 0.0, prmse = 0.0;
+  int it = 0, st = 2;
+  for (;; it++) {  // at most max_iters + 1 evaluations
+    // ---- Evaluate(T): nearest targets, M, E and the centroid sums
+    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int tile = 0; tile < tiles; tile++) {
+      const int s0 = tile * kITile;
+      float m[kIP][3], bd[kIP];
+#pragma unroll
+      for (int k = 0; k < kIP; k++) {
+        const int i = s0 + k * kIT + tid;
+        if (i < n1) {
+#pragma unroll
+          for (int d = 0; d < 3; d++) a[k][d] = A[(size_t)d * n1 + i];
+          pcr_rigid_apply(T, a[k][0], a[k][1], a[k][2], m[k]);
+        } else {
+          a[k][0] = a[k][1] = a[k][2] = 0.0f;
+          m[k][0] = m[k][1] = m[k][2] = __builtin_nanf("");
+        }
+        bd[k] = __builtin_inff();
+        bj[k] = -1;
+      }
+      const bool any = s0 + tid < n1;  // k = 0 is the thread's lowest point
+      if (whole) {
+        if (any) icp_scan(tg, cap, 0, n2, m, bd, bj);
+      } else {
+        for (int c0 = 0; c0 < n2; c0 += cap) {
+          const int len = min(cap, n2 - c0);
+          lds_barrier();
+          icp_stage(tg, cap, B, n2, c0, len);
+          lds_barrier();
+          if (any) icp_scan(tg, cap, c0, len, m, bd, bj);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kIP; k++) {
+        const int i = s0 + k * kIT + tid;
+        if (!(bj[k] >= 0 && bd[k] <= tau2)) bj[k] = -1;
+        if (bj[k] >= 0) {
+#pragma unroll
+          for (int d = 0; d < 3; d++)
+            b[k][d] = whole ? tg[d * cap + bj[k]] : B[(size_t)d * n2 + bj[k]];
+          acc[0] += 1.0;
+          acc[1] += (double)bd[k];
+#pragma unroll
+          for (int d = 0; d < 3; d++) {
+            acc[2 + d] += (double)a[k][d];
+            acc[5 + d] += (double)b[k][d];
+          }
+        }
+        if (!kResident && i < n1) cq[i] = bj[k];
+      }
+    }
+    icp_block_sum(acc, red_s);
+    M = acc[0];
+    E = acc[1];
+    const double fit = M / (double)n1;
+    const double rm = M > 0.0 ? __builtin_sqrt(E / M) : 0.0;
+    const bool conv = it > 0 && __builtin_fabs(pfit - fit) < rel_fitness &&
+                      __builtin_fabs(prmse - rm) < rel_rmse;
+    pfit = fit;
+    prmse = rm;
+    // every exit is uniform: the sums are the same bits in every thread
+    if (conv) {
+      st = 0;
+      break;
+    }
+    if (it >= max_iters) break;
+    if (M < 3.0) {
+      st = 1;
+      break;
+    }
+    // ---- least squares over the correspondences, from the original points
+    double ca[3], cb[3], cov[9];
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      ca[d] = acc[2 + d] / M;
+      cb[d] = acc[5 + d] / M;
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) cov[i] = 0.0;
+    for (int tile = 0; tile < tiles; tile++) {
+#pragma unroll
+      for (int k = 0; k < kIP; k++) {
+        if (!kResident) {
+          const int i = tile * kITile + k * kIT + tid;
+          bj[k] = i < n1 ? cq[i] : -1;  // this thread's own store
+          if (bj[k] >= 0) {
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+              a[k][d] = A[(size_t)d * n1 + i];
+              b[k][d] = B[(size_t)d * n2 + bj[k]];
+            }
+          }
+        }
+        if (bj[k] >= 0) {
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+              cov[3 * i + j] += ((double)a[k][i] - ca[i]) * ((double)b[k][j] - cb[j]);
+        }
+      }
+    }
+    icp_block_sum(cov, red_s);
+    if (tid < kWave) {
+      pcr_rigid_from_cov(ca, cb, cov, R, t);
+      if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) sol_s[i] = R[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) sol_s[9 + i] = t[i];
+      }
+    }
+    lds_barrier();
+#pragma unroll
+    for (int i = 0; i < 9; i++) R[i] = sol_s[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) t[i] = sol_s[9 + i];
+    pcr_rigid_round(R, t, T);
+  }
+
+  if (kResident) {
+#pragma unroll
+    for (int k = 0; k < kIP; k++) {
+      const int i = k * kIT + tid;
+      if (i < n1) cq[i] = bj[k];
+    }
+  }
+  if (tid == 0) {
+    double* tq = transform + (size_t)q * 16;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      tq[4 * i] = R[3 * i];
+      tq[4 * i + 1] = R[3 * i + 1];
+      tq[4 * i + 2] = R[3 * i + 2];
+      tq[4 * i + 3] = t[i];
+    }
+    tq[12] = 0.0;
+    tq[13] = 0.0;
+    tq[14] = 0.0;
+    tq[15] = 1.0;
+    num_corr[q] = (int)M;
+    fitness[q] = pfit;
+    rmse[q] = prmse;
+    iterations[q] = it;
+    status[q] = st;
+  }
+}
+
+}  // namespace pcr
+
+using namespace pcr;
+
+extern "C" pcr_status pcr_icp_point_to_point(const float* xyz1, const float* xyz2, int p, int n1,
+                                             int n2, const double* init, float max_dist,
+                                             int max_iters, double rel_fitness, double rel_rmse,
+                                             double* transform, int* corr, int* num_corr,
+                                             double* fitness, double* rmse, int* iterations,
+                                             int* status, void* stream) {
+  PCR_REQUIRE(p >= 0 && n1 >= 1 && n2 >= 1, "icp_point_to_point: invalid sizes");
+  PCR_REQUIRE(max_dist > 0.0f, "icp_point_to_point: max_dist must be positive");
+  PCR_REQUIRE(max_iters >= 0 && max_iters <= kIcpMaxIters,
+              "icp_point_to_point: max_iters (%d) outside [0, %d]", max_iters, kIcpMaxIters);
+  PCR_REQUIRE(rel_fitness >= 0.0 && rel_rmse >= 0.0,
+              "icp_point_to_point: negative or NaN tolerance");
+  if (p == 0) return PCR_OK;
+  PCR_REQUIRE(xyz1 && xyz2 && transform && corr && num_corr && fitness && rmse && iterations &&
+                  status,
+              "icp_point_to_point: null pointer");
+  hipStream_t st = as_stream(stream);
+  const int cap = icp_cap(n2);
+  const size_t lds = icp_lds_bytes(cap);
+  const float tau2 = max_dist * max_dist;
+  if (n1 <= kITile) {
+    allow_big_lds(icp_kernel<true>, lds);
+    hipLaunchKernelGGL(icp_kernel<true>, dim3(p), dim3(kIT), lds, st, xyz1, xyz2, n1, n2, init,
+                       tau2, max_iters, rel_fitness, rel_rmse, cap, transform, corr, num_corr,
+                       fitness, rmse, iterations, status);
+  } else {
+    allow_big_lds(icp_kernel<false>, lds);
+    hipLaunchKernelGGL(icp_kernel<false>, dim3(p), dim3(kIT), lds, st, xyz1, xyz2, n1, n2, init,
+                       tau2, max_iters, rel_fitness, rel_rmse, cap, transform, corr, num_corr,
+                       fitness, rmse, iterations, status);
+  }
+  return launch_status("icp_point_to_point");
+}

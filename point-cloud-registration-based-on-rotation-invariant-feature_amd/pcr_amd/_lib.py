@@ -76,6 +76,8 @@ SIGNATURES = {
     "pcr_rigid_ransac_workspace_size": (SZ, [I, I, I]),
     "pcr_rigid_ransac": (ST, [P, P, I, I, I, P, P, P, I, F, F, I, ctypes.c_uint, P, P, P, P, P, P,
                              P, SZ, P]),
+    "pcr_icp_point_to_point": (ST, [P, P, I, I, I, P, F, I, ctypes.c_double, ctypes.c_double, P, P,
+                                   P, P, P, P, P, P]),
     "pcr_lrf_change_coords": (ST, [P, I, I, P, P, P, P, P]),
     "pcr_gather_features_forward": (ST, [P, P, I, I, I, I, P, P]),
     "pcr_gather_features_backward": (ST, [P, P, I, I, I, I, P, P]),

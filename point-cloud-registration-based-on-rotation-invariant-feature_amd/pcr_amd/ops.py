@@ -560,3 +560,38 @@ def rigid_ransac(xyz1, xyz2, idx1, idx2, count, hyps=1000, inlier_dist=0.08, edg
         _ptr(status), _ptr(ws), ws.numel(), _stream()), "rigid_ransac")
     out = (transform, inliers, num_inliers, best_hyp, status)
     return out + (scores,) if return_scores else out
+
+
+def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, rel_rmse=1e-6):
+    """Point-to-point ICP of p registration pairs (utils/open3d_func.py:63-72,
+    register_one_pair(func='icp'), batched; the defaults are its distance 0.2
+    and 200 iterations with Open3D's default convergence criteria): xyz1
+    [p, 3, n1] source, xyz2 [p, 3, n2] target, init [p, 4, 4] float64 (None:
+    the identity) -> (transform [p, 4, 4] fp64 with xyz2 ~ R xyz1 + t, corr
+    [p, n1] nearest target within max_dist or -1, num_corr [p], fitness [p],
+    rmse [p], iterations [p], status [p]: 0 converged, 1 fewer than 3
+    correspondences, 2 iteration limit).  max_iters = 0 evaluates init.  The
+    whole loop runs on the device; bit-identical from run to run."""
+    _check(xyz1, "xyz1")
+    _check(xyz2, "xyz2")
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
+            xyz1.shape[0] != xyz2.shape[0]:
+        raise RuntimeError("icp: expected [p, 3, n] clouds with equal pair counts")
+    p, _, n1 = xyz1.shape
+    n2 = xyz2.shape[2]
+    if init is not None:
+        _check(init, "init", None)
+        if init.dtype != torch.float64 or tuple(init.shape) != (p, 4, 4):
+            raise RuntimeError("icp: init must be a float64 [p, 4, 4] tensor")
+    dev = xyz1.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    transform = torch.empty((p, 4, 4), **f64)
+    corr = torch.empty((p, n1), **i32)
+    num_corr, iterations, status = (torch.empty((p,), **i32) for _ in range(3))
+    fitness, rmse = torch.empty((p,), **f64), torch.empty((p,), **f64)
+    _lib.check(_lib.load().pcr_icp_point_to_point(
+        _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(init), float(max_dist), int(max_iters),
+        float(rel_fitness), float(rel_rmse), _ptr(transform), _ptr(corr), _ptr(num_corr),
+        _ptr(fitness), _ptr(rmse), _ptr(iterations), _ptr(status), _stream()), "icp")
+    return transform, corr, num_corr, fitness, rmse, iterations, status

@@ -19,7 +19,10 @@ one step of a rank's shard of P pairs is:
 The correspondences become a rigid transform per pair on the device too
 (ops.rigid_ransac: a seeded RANSAC + least-squares refit):
 PairExtractor.register, or register_pairs for features from elsewhere;
-rre_rte are the reference's error meters.
+rre_rte and alignment_rmse are the reference's error meters.  ops.icp (the
+reference's func='icp' solver) re-fits a transform over every
+point within a distance: icp_pairs on its own, or `icp=` of register /
+register_pairs as the refinement of the RANSAC estimate.
 
 The native runner (pcr_extractor_run with match_pairs = P) enqueues the
 matching on each step's voxel queue right after its devox (behind the grid
@@ -103,32 +106,60 @@ class PairExtractor:
     def reserve_timing(self, timed_steps):
         self.ex.reserve_timing(timed_steps)
 
-    def register(self, xyz, normals, features, **ransac):
+    def register(self, xyz, normals, features, icp=None, **ransac):
         """forward, then the rigid transform of every pair from its
         correspondences (ops.rigid_ransac on the current stream; `ransac`:
         its keyword arguments): forward's keys plus transform [P, 4, 4] fp64
         (target ~ R source + t), inliers, num_inliers, best_hyp and
-        reg_status."""
+        reg_status.  icp: a dict of ops.icp keywords (may be empty) refines
+        that transform by point-to-point ICP into the icp_* keys of
+        register_pairs."""
         out = self.forward(xyz, normals, features)
         p = self.pairs
         got = ops.rigid_ransac(xyz[:p], xyz[p:], out["idx1"], out["idx2"], out["count"], **ransac)
         out.update(zip(("transform", "inliers", "num_inliers", "best_hyp", "reg_status"), got))
+        if icp is not None:
+            out.update(_icp_refine(xyz[:p], xyz[p:], out["transform"], icp))
         return out
 
 
-def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, **ransac):
+ICP_KEYS = ("transform", "corr", "num_corr", "fitness", "rmse", "iterations", "status")
+
+
+def icp_pairs(xyz1, xyz2, init=None, **icp):
+    """register_one_pair(func='icp') (utils/open3d_func.py:63-72), batched
+    and on the device: xyz1 [p, 3, n1], xyz2 [p, 3, n2], init [p, 4, 4]
+    float64 or None -> ops.icp's outputs as a dict (transform, corr, num_corr,
+    fitness, rmse, iterations, status); `icp`: its keyword arguments."""
+    return dict(zip(ICP_KEYS, ops.icp(xyz1, xyz2, init, **icp)))
+
+
+def _icp_refine(xyz1, xyz2, transform, icp):
+    """ICP from `transform` (pairs whose RANSAC failed carry the identity)
+    -> the icp_* keys"""
+    got = ops.icp(xyz1, xyz2, transform, **icp)
+    return {"icp_" + k: v for k, v in zip(ICP_KEYS, got)}
+
+
+def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **ransac):
     """Pair in, transform out (datasets/deepgmr_mn40.py:165-244,
     find_correspondence_one_pair + register_one_pair(func='ransac'), batched
     and on the device): xyz1 [p, 3, n1], xyz2 [p, 3, n2] and per-point
     features [p, n, c] (channel_major: [p, c, n]) -> a dict with the matching
     (idx1, idx2, count) and ops.rigid_ransac's outputs (transform, inliers,
     num_inliers, best_hyp, reg_status; scores with return_scores).  The
-    correspondence count never visits the host."""
+    correspondence count never visits the host.  icp: a dict of ops.icp
+    keywords (may be empty) refines the RANSAC transform by point-to-point
+    ICP over every point; its outputs come as icp_transform, icp_corr,
+    icp_num_corr, icp_fitness, icp_rmse, icp_iterations and icp_status, the
+    other keys are unchanged."""
     _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
     got = ops.rigid_ransac(xyz1, xyz2, idx1, idx2, count, **ransac)
     out = {"idx1": idx1, "idx2": idx2, "count": count}
     out.update(zip(("transform", "inliers", "num_inliers", "best_hyp", "reg_status", "scores"),
                    got))
+    if icp is not None:
+        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp))
     return out
 
 
@@ -149,3 +180,11 @@ def rre_rte(gt, est):
     rre = torch.rad2deg(torch.acos(torch.clamp((tr - 1.0) / 2.0, -1.0, 1.0)))
     rte = torch.linalg.norm(gt[:, :3, 3] - est[:, :3, 3], dim=1)
     return rre, rte
+
+
+def alignment_rmse(xyz1, gt, est):
+    """The reference meter's rmse (datasets/deepgmr_mn40.py:124-126), batched:
+    the mean over the points of [p, 3, n] clouds of |est p - gt p|, fp64 [p]."""
+    gt, est = gt.to(torch.float64), est.to(torch.float64)
+    return torch.linalg.norm(apply_transform(xyz1, est) - apply_transform(xyz1, gt), dim=1).mean(
+        dim=1)
