@@ -469,32 +469,41 @@ pcr_status pcr_read_xyzn_txt(const char *path, float *out, long long rows, int c
  * measures), enqueued from native code: every launch and cross-stream event
  * of every step is issued here, so the host enqueue rate never limits the
  * step rate.  Forked from and joined back into `origin`.
+ *
+ * Step s of a call reads its clouds from, and writes every output into,
+ * sets[(set0 + s) % nsets] -- a fresh batch per step, as the reference's
+ * loaders hand one over per iteration (datasets/deepgmr_mn40.py:71-97,
+ * train.py:138-153); nsets = 1 runs every step over one set of buffers.  The
+ * workspaces are per queue, not per set.  With steps <= nsets every step of
+ * a call writes its own set, so after the call (all streams joined back into
+ * `origin`) the outputs of every step are readable on `origin`; the next
+ * call forks from `origin` after whatever the caller enqueued there, so a
+ * consumer enqueued between calls never races the next call's writes.  More
+ * steps than sets in one call overwrite set q with step s + nsets.
+ * desc_steps: [steps][b][c] per-step descriptors, or NULL (then each set's
+ * desc).
  *   schedule 0: serial, two streams -- s_nbr: Morton sort, KNN selection,
- *               local PPF; s_vox: prep + the fused grid / devox / descriptor
- *               kernel; the single set of buffers (or ring set s).
+ *               local PPF with knn_ws[0]; s_vox: prep + the fused grid /
+ *               devox / descriptor kernel with vox_ws[0].
  *   (schedules 1-5, single-queue-per-stage variants measured in rounds 2-4,
  *   were removed: DESIGN.md 4.)
  *   schedule 6: two independent pipelines per chain and no cross-queue event
  *               inside the run: the voxel chain (prep, means / devox /
  *               descriptor, matching, grid stream) of step s on s_vox (even
- *               s) or `origin` (odd s) with voxel workspace s % 2, the KNN
- *               chain (sort, selection, local PPF) on s_nbr (even) or s_pre
- *               (odd) with KNN workspace s % 2, so every workspace is reused
- *               only on its own queue.  The odd voxel queue starts after step
- *               0's means (one wait per call) so the two grid streams
- *               alternate rather than coincide.  Needs a batch ring of >= 2
- *               sets (consecutive steps write distinct sets); a ring of odd
- *               size that one call wraps orders each set's rewrite behind its
- *               previous step with per-set events (made on first use).
- *   schedule 7: as 6 with three voxel queues (s_vox, origin, s_pre: voxel
- *               workspaces vox_ws[0], vox_ws[1], vox_ws3) and one KNN queue
- *               (s_nbr); needs a ring of >= 3 sets, per-set events when the
- *               ring size is not a multiple of 3.  Schedules 6 / 7 with
- *               match_pairs: each voxel queue matches in its own part (half
- *               / third) of match_ws.
- * Buffers with two entries: schedule 0 uses entry 0; schedules 6 / 7 use
- * knn_ws[q] / vox_ws[q] (+ vox_ws3) as the queue's workspace.
- * desc_steps: [steps][b][c] per-step descriptors, or NULL (then desc).
+ *               s) or `origin` (odd s) with vox_ws[s % 2], the KNN chain
+ *               (sort, selection, local PPF) on s_nbr (even) or s_pre (odd)
+ *               with knn_ws[s % 2], so every workspace is reused only on its
+ *               own queue.  The odd voxel queue starts after step 0's means
+ *               (one wait per call) so the two grid streams alternate rather
+ *               than coincide.  Needs nsets >= 2 (consecutive steps write
+ *               distinct sets); a ring of odd size that one call wraps orders
+ *               each set's rewrite behind its previous step with per-set
+ *               events (made on first use).
+ *   schedule 7: as 6 with three voxel queues (s_vox, origin, s_pre with
+ *               vox_ws[0..2]) and one KNN queue (s_nbr, knn_ws[0]); needs
+ *               nsets >= 3, per-set events when the ring size is not a
+ *               multiple of 3.  Schedules 6 / 7 with match_pairs: each voxel
+ *               queue matches in its own part (half / third) of match_ws.
  *
  * `runner` holds the run's cross-stream events, created once by
  * pcr_runner_create on the current device and reused by every call (NULL:
@@ -503,19 +512,7 @@ pcr_status pcr_read_xyzn_txt(const char *path, float *out, long long rows, int c
  * min(steps, timed_steps) steps in the middle of each run (pipeline full; fewer after
  * pcr_runner_set_timed) with timing events on its stream;
  * pcr_runner_grid_times waits for them and returns the per-step durations
- * (ms) of the last run -- the dominant kernel's in-step duration.
- *
- * Batch ring (nsets > 0; required by schedules 6 and 7): step s of a call reads its clouds
- * from, and writes every output into, sets[(set0 + s) % nsets] -- a fresh
- * batch per step, as the reference's loaders hand one over per iteration
- * (datasets/deepgmr_mn40.py:71-97, train.py:138-153) -- and the single-set
- * input / output pointers of pcr_extractor_args are ignored (the workspaces
- * stay per queue).  With steps <= nsets every step of a
- * call writes its own set, so after the call (all streams joined back into
- * `origin`) the outputs of every step are readable on `origin`; the next
- * call forks from `origin` after whatever the caller enqueued there, so a
- * consumer enqueued between calls never races the next call's writes.  More
- * steps than sets in one call overwrite set q with step s + nsets. */
+ * (ms) of the last run -- the dominant kernel's in-step duration. */
 typedef struct pcr_runner pcr_runner;
 pcr_status pcr_runner_create(int timed_steps, pcr_runner **out);
 void pcr_runner_destroy(pcr_runner *runner);
@@ -523,6 +520,7 @@ pcr_status pcr_runner_grid_times(pcr_runner *runner, float *ms, int cap, int *co
 /* steps timed by each later run (0..timed_steps of pcr_runner_create; the
  * default is all of them) */
 pcr_status pcr_runner_set_timed(pcr_runner *runner, int timed_steps);
+/* the clouds and outputs of one step */
 typedef struct pcr_extractor_set {
   const float *xyz, *normals, *features;  /* [b,3,n], [b,3,n], [b,c,n] */
   int *knn_idx;                           /* [b,k,n] */
@@ -535,39 +533,27 @@ typedef struct pcr_extractor_set {
   float *dwgts;                           /* [b,8,n] */
   int *corr12, *corr21, *idx1, *idx2, *match_count; /* match_pairs > 0: [P,n] / [P] */
 } pcr_extractor_set;
+/* what holds for every step of a run */
 typedef struct pcr_extractor_args {
   int b, n, c, k, r, relative;
-  const float *xyz, *normals, *features;  /* [b,3,n], [b,3,n], [b,c,n] */
-  int *knn_idx;                           /* [b,k,n] */
-  float *knn_dist;                        /* [b,k,n] or NULL */
-  float *local_ppf;                       /* [b,4,k,n] */
-  float *norm_coords;                     /* [b,3,n] */
-  int *ind, *cnt;                         /* [b,n], [b,r^3] */
-  float *grid, *devox, *desc;             /* [b,c,r^3], [b,c,n], [b,c] */
-  int *dinds[2];                          /* [b,8,n] */
-  float *dwgts[2];                        /* [b,8,n] */
   void *knn_ws[2];                        /* pcr_knn_workspace_size(b, n, n) */
   size_t knn_ws_bytes;
-  void *vox_ws[2];                        /* pcr_extractor_workspace_size(b, n, c, r) */
+  void *vox_ws[3];                        /* pcr_extractor_workspace_size(b, n, c, r) */
   size_t vox_ws_bytes;
   /* registration pairs (BASELINE c4, datasets/deepgmr_mn40.py:71-97,
    * 232-244): match_pairs = P > 0 with b == 2P makes every step also match
    * the devoxelised per-point features of cloud i (source) against cloud
-   * P + i (target) by pcr_mutual_nn_match_cm, on the prep stream after the
-   * step's devox; outputs [P, n] (count [P]) as that function's. */
+   * P + i (target) by pcr_mutual_nn_match_cm, on the step's voxel queue
+   * after its devox, into its set's corr12 ... match_count. */
   int match_pairs;
-  int *corr12, *corr21, *idx1, *idx2, *match_count;
   void *match_ws;                         /* pcr_mutual_nn_workspace_size(P, n, n);
                                              schedules 6 / 7: two / three times
                                              that + 512 B (one part per voxel
                                              queue) */
   size_t match_ws_bytes;
-  /* batch ring (see above): nsets sets, step s of the call uses set
-   * (set0 + s) % nsets; nsets = 0: the single set above */
+  /* nsets >= 1 sets; step s of the call uses set (set0 + s) % nsets */
   int nsets, set0;
   const pcr_extractor_set *sets;
-  /* schedule 7: the third voxel workspace (vox_ws_bytes) */
-  void *vox_ws3;
   /* nonzero: the spherical devox + descriptor stay in the means launch
    * (pcr_extractor_voxel_means_devox + pcr_extractor_voxel_stream) even where
    * the grid stream could evaluate them (pcr_extractor_stream_devox_ok); 0

@@ -68,46 +68,18 @@ namespace {
     }                                                                            \
   } while (0)
 
-// The inputs and outputs of one step: the single set of pcr_extractor_args
-// (nsets = 0, devox corners alternating with the scratch slot) or the batch
-// ring's set (set0 + s) % nsets
-struct StepIO {
-  const float *xyz, *normals, *features;
-  int* knn_idx;
-  float *knn_dist, *local_ppf, *norm_coords;
-  int *ind, *cnt;
-  float *grid, *devox, *desc;
-  int* dinds;
-  float* dwgts;
-  int *corr12, *corr21, *idx1, *idx2, *match_count;
-};
-
-StepIO step_io(const pcr_extractor_args* a, int s, int slot) {
-  if (a->nsets > 0) {
-    const pcr_extractor_set& t = a->sets[(a->set0 + s) % a->nsets];
-    return StepIO{t.xyz,  t.normals,     t.features, t.knn_idx, t.knn_dist, t.local_ppf,
-                  t.norm_coords, t.ind,  t.cnt,      t.grid,    t.devox,    t.desc,
-                  t.dinds, t.dwgts,      t.corr12,   t.corr21,  t.idx1,     t.idx2,
-                  t.match_count};
-  }
-  return StepIO{a->xyz,  a->normals,     a->features,     a->knn_idx, a->knn_dist, a->local_ppf,
-                a->norm_coords, a->ind,  a->cnt,          a->grid,    a->devox,    a->desc,
-                a->dinds[slot], a->dwgts[slot], a->corr12, a->corr21, a->idx1,     a->idx2,
-                a->match_count};
-}
-
 // Morton sort of the cloud into KNN workspace q; false when the sorted path
 // does not apply (nothing launched; the selection then runs unsorted)
-pcr_status knn_sort(const pcr_extractor_args* a, const StepIO& io, int q, hipStream_t st,
-                    bool* sorted) {
+pcr_status knn_sort(const pcr_extractor_args* a, const pcr_extractor_set& io, int q,
+                    hipStream_t st, bool* sorted) {
   const pcr_status rc = pcr_knn_prepare(io.xyz, a->b, a->n, a->knn_ws[q], a->knn_ws_bytes, st);
   *sorted = rc == PCR_OK;
   return rc == PCR_ERR_UNSUPPORTED ? PCR_OK : rc;
 }
 
 // selection (from KNN workspace q) + local PPF of one step on `st`
-pcr_status knn_select_ppf(const pcr_extractor_args* a, const StepIO& io, int q, bool sorted,
-                          hipStream_t st) {
+pcr_status knn_select_ppf(const pcr_extractor_args* a, const pcr_extractor_set& io, int q,
+                          bool sorted, hipStream_t st) {
   if (!sorted)  // no sorted path: the one-call selection + PPF
     return pcr_knn_local_ppf(io.xyz, io.normals, a->b, a->n, a->k, a->relative, io.knn_idx,
                              io.knn_dist, io.local_ppf, a->knn_ws[q], a->knn_ws_bytes, st);
@@ -120,7 +92,7 @@ pcr_status knn_select_ppf(const pcr_extractor_args* a, const StepIO& io, int q, 
 // the step's registration matching (source clouds [0, P) against targets
 // [P, 2P)) on the devox features the step just wrote; nparts > 1: schedules
 // 6 / 7, whose voxel queues each match in their own part of the workspace
-pcr_status match_pairs(const pcr_extractor_args* a, const StepIO& io, hipStream_t st,
+pcr_status match_pairs(const pcr_extractor_args* a, const pcr_extractor_set& io, hipStream_t st,
                        int part = 0, int nparts = 1) {
   if (a->match_pairs <= 0) return PCR_OK;
   const int P = a->match_pairs;
@@ -218,8 +190,8 @@ extern "C" pcr_status pcr_extractor_run(pcr_runner* runner, const pcr_extractor_
   if (steps == 0 || a->b == 0) return PCR_OK;
   const hipStream_t org = as_stream(origin), sn = as_stream(s_nbr_p), sp = as_stream(s_pre_p),
                     sv = as_stream(s_vox_p);
-  PCR_REQUIRE(a->nsets >= 0 && (a->nsets == 0 || (a->sets && a->set0 >= 0)),
-              "extractor_run: a batch ring needs sets and set0 >= 0");
+  PCR_REQUIRE(a->nsets >= 1 && a->sets != nullptr && a->set0 >= 0,
+              "extractor_run: needs sets (nsets >= 1 of pcr_extractor_set) and set0 >= 0");
   // schedules 6 / 7: nvq voxel queues and nkq KNN queues, each running a
   // whole chain of every nvq-th / nkq-th step
   const int nvq = schedule == 7 ? 3 : 2, nkq = schedule == 7 ? 1 : 2;
@@ -228,8 +200,7 @@ extern "C" pcr_status pcr_extractor_run(pcr_runner* runner, const pcr_extractor_
   // consecutive steps are written from different queues: they need distinct
   // output sets (the c5 voxel path counts into cnt with atomics)
   PCR_REQUIRE(!multi || a->nsets >= nvq,
-              "extractor_run: schedule %d needs a batch ring of at least %d sets", schedule,
-              nvq);
+              "extractor_run: schedule %d needs at least %d sets", schedule, nvq);
   // the voxel queues match at once: each part of the matching workspace
   // must hold one matching
   PCR_REQUIRE(!multi || a->match_pairs <= 0 ||
@@ -237,20 +208,16 @@ extern "C" pcr_status pcr_extractor_run(pcr_runner* runner, const pcr_extractor_
                       pcr_mutual_nn_workspace_size(a->match_pairs, a->n, a->n),
               "extractor_run: schedule %d with match_pairs needs a matching workspace of "
               "%d x pcr_mutual_nn_workspace_size (plus 512 B)", schedule, nvq);
-  PCR_REQUIRE(schedule != 7 || a->vox_ws3 != nullptr,
-              "extractor_run: schedule 7 needs the third voxel workspace (vox_ws3)");
-  void* const vws[3] = {a->vox_ws[0], a->vox_ws[1], a->vox_ws3};
   for (int q = 0; q < nvws; q++)
-    PCR_REQUIRE(vws[q] != nullptr, "extractor_run: voxel workspace %d missing", q);
+    PCR_REQUIRE(a->vox_ws[q] != nullptr, "extractor_run: voxel workspace %d missing", q);
   for (int q = 0; q < nkws; q++)
     PCR_REQUIRE(a->knn_ws[q] != nullptr, "extractor_run: KNN workspace %d missing", q);
-  PCR_REQUIRE(a->nsets > 0 || (a->dinds[0] && a->dwgts[0]),
-              "extractor_run: devox corner buffers missing");
   for (int t = 0; t < a->nsets; t++)
     PCR_REQUIRE(a->sets[t].xyz && a->sets[t].normals && a->sets[t].features &&
                     a->sets[t].knn_idx && a->sets[t].local_ppf && a->sets[t].grid &&
                     a->sets[t].devox && a->sets[t].dinds && a->sets[t].dwgts,
-                "extractor_run: ring set %d incomplete", t);
+                "extractor_run: set %d incomplete (needs xyz, normals, features, knn_idx, "
+                "local_ppf, grid, devox, dinds, dwgts)", t);
   // no runner: a transient one (events created and destroyed in this call;
   // hipEventDestroy of a pending event is deferred until it completes)
   pcr_runner* tmp = nullptr;
@@ -273,8 +240,8 @@ extern "C" pcr_status pcr_extractor_run(pcr_runner* runner, const pcr_extractor_
   // schedules 6 / 7 over a ring that one call wraps onto other queues
   // (nsets not a multiple of the queue count): per-set events, made once
   // per ring size (the first call, outside any timed region)
-  const bool ring_wait = multi && a->nsets > 0 && steps > a->nsets &&
-                         (a->nsets % nvq != 0 || a->nsets % nkq != 0);
+  const bool ring_wait =
+      multi && steps > a->nsets && (a->nsets % nvq != 0 || a->nsets % nkq != 0);
   if (ring_wait && rn->ring_ev.size() != (size_t)(2 * a->nsets)) {
     for (hipEvent_t ev : rn->ring_ev)
       if (ev) (void)hipEventDestroy(ev);
@@ -286,7 +253,8 @@ extern "C" pcr_status pcr_extractor_run(pcr_runner* runner, const pcr_extractor_
   for (hipStream_t st : {sn, sp, sv}) PCR_HIP(hipStreamWaitEvent(st, fork, 0), "fork wait");
   const size_t dstride = (size_t)a->b * a->c;
   for (int s = 0; s < steps; s++) {
-    const StepIO io = step_io(a, s, 0);
+    const int t = (a->set0 + s) % a->nsets;
+    const pcr_extractor_set& io = a->sets[t];
     float* desc = desc_steps ? desc_steps + (size_t)s * dstride : io.desc;
     bool sorted = false;
     if (schedule == 0) {
@@ -309,8 +277,7 @@ extern "C" pcr_status pcr_extractor_run(pcr_runner* runner, const pcr_extractor_
     const hipStream_t vqs[3] = {sv, org, sp}, kqs[2] = {sn, sp};
     const int iv = s % nvq, ik = s % nkq;
     const hipStream_t vq = vqs[iv], kq = kqs[ik];
-    void* const vw6 = vws[iv];
-    const int t = a->nsets > 0 ? (a->set0 + s) % a->nsets : 0;
+    void* const vw6 = a->vox_ws[iv];
     hipEvent_t* const rv = ring_wait ? rn->ring_ev.data() : nullptr;
     if (rv && s >= a->nsets) {  // set t last written on the other queues
       PCR_HIP(hipStreamWaitEvent(vq, rv[2 * t], 0), "ring wait");

@@ -30,7 +30,7 @@ pcr_status launch_status(const char* what) {
 
 extern "C" const char* pcr_last_error(void) { return pcr::g_err; }
 
-extern "C" const char* pcr_version(void) { return "pcr_amd 0.1.0 gfx950"; }
+extern "C" const char* pcr_version(void) { return "pcr_amd 0.2.0 gfx950"; }
 
 // A stream whose kernels run only on the CUs set in `mask` (nwords 32-bit
 // words, bit i = CU i in the runtime's CU numbering), e.g. to keep the

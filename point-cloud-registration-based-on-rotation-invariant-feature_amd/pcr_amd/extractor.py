@@ -43,24 +43,18 @@ class SphExtractor:
         # means launch, in the eager / pipelined paths and in the native
         # runner (pcr_extractor_args.devox_in_means)
         self.stream_devox = stream_devox
+        self._runner, self._runner_cap = None, 0  # before anything can raise: __del__
         self.b, self.n, self.c, self.k, self.r = batch, npoints, channels, k, resolution
         self.relative = relative
         self.device = torch.device(device)
         b, n, c, r = batch, npoints, channels, resolution
-        r3 = r * r * r
         dev = self.device
         e = torch.empty
-        self.knn_idx = e((b, k, n), dtype=torch.int32, device=dev)
-        self.knn_dist = e((b, k, n), dtype=torch.float32, device=dev) if with_dist else None
-        self.local_ppf = e((b, 4, k, n), dtype=torch.float32, device=dev)
-        self.norm_coords = e((b, 3, n), dtype=torch.float32, device=dev)
-        self.ind = e((b, n), dtype=torch.int32, device=dev)
-        self.cnt = e((b, r3), dtype=torch.int32, device=dev)
-        self.grid = e((b, c, r3), dtype=torch.float32, device=dev)
-        self.devox = e((b, c, n), dtype=torch.float32, device=dev)
-        self.dinds = e((b, 8, n), dtype=torch.int32, device=dev)
-        self.dwgts = e((b, 8, n), dtype=torch.float32, device=dev)
-        self.desc = e((b, c), dtype=torch.float32, device=dev)
+        # self.knn_idx, local_ppf, norm_coords, ind, cnt, grid, devox, desc,
+        # dinds, dwgts (and knn_dist with with_dist)
+        self.knn_dist = None
+        for name, shape, dtype in self._step_outputs(with_dist):
+            setattr(self, name, e(shape, dtype=dtype, device=dev))
         lib = _lib.load()
         self.ws = e(max(256, lib.pcr_extractor_workspace_size(b, n, c, r)), dtype=torch.uint8,
                     device=dev)
@@ -71,13 +65,30 @@ class SphExtractor:
         self.s_vox = torch.cuda.Stream(device=dev)
         self.s_dev = torch.cuda.Stream(device=dev)
         self.graph = None
-        self._runner, self._runner_cap = None, 0
         self._static_in = None
         self._set1 = None
         self._vsep, self._vset1 = False, None
         self._ppf1 = None
+        self._ws3 = None  # the third voxel workspace of runner schedule 7
         self._args, self._args_key = None, None
+        self._ring, self._ring_match = None, 0
         self._ring_seen = None  # (batch tuples, match, args key) of the last run_ring
+
+    def _step_outputs(self, with_dist, match_pairs=0):
+        """(name, shape, dtype) of every output of a step: the output fields
+        of pcr_extractor_set (include/pcr_amd.h; count is its match_count)."""
+        b, n, c, k, r3 = self.b, self.n, self.c, self.k, self.r ** 3
+        i32, f32 = torch.int32, torch.float32
+        table = [("knn_idx", (b, k, n), i32), ("local_ppf", (b, 4, k, n), f32),
+                 ("norm_coords", (b, 3, n), f32), ("ind", (b, n), i32), ("cnt", (b, r3), i32),
+                 ("grid", (b, c, r3), f32), ("devox", (b, c, n), f32), ("desc", (b, c), f32),
+                 ("dinds", (b, 8, n), i32), ("dwgts", (b, 8, n), f32)]
+        if with_dist:
+            table.append(("knn_dist", (b, k, n), f32))
+        if match_pairs:
+            table += [(key, (match_pairs, n), i32) for key in ("corr12", "corr21", "idx1", "idx2")]
+            table.append(("count", (match_pairs,), i32))
+        return table
 
     # ---------------------------------------------------------------- stages
     # Buffers a later stage of the same step reads (the two workspaces and the
@@ -538,7 +549,7 @@ class SphExtractor:
         self._get_runner(int(timed_steps))
 
     def _free_runner(self):
-        if getattr(self, "_runner", None) is not None:
+        if self._runner is not None:
             torch.cuda.synchronize(self.device)
             _lib.load().pcr_runner_destroy(self._runner)
         self._runner, self._runner_cap = None, 0
@@ -560,58 +571,57 @@ class SphExtractor:
                                                      ctypes.byref(cnt)), "runner_grid_times")
         return list(ms[:cnt.value])
 
-    def _make_args(self, xyz, normals, features, match):
-        """pcr_extractor_args (include/pcr_amd.h) over these inputs and the
-        extractor's buffers."""
-        s1 = self._set(1)
+    def _make_args(self, steps_io, match):
+        """pcr_extractor_args (include/pcr_amd.h) with one pcr_extractor_set
+        per ((xyz, normals, features), outputs dict) of steps_io."""
         a = _lib.ExtractorArgs()
         a.b, a.n, a.c, a.k, a.r, a.relative = self.b, self.n, self.c, self.k, self.r, \
             int(self.relative)
-        a.xyz, a.normals, a.features = _ptr(xyz), _ptr(normals), _ptr(features)
-        a.knn_idx, a.knn_dist, a.local_ppf = _ptr(self.knn_idx), _ptr(self.knn_dist), \
-            _ptr(self.local_ppf)
-        a.norm_coords, a.ind, a.cnt, a.grid = _ptr(self.norm_coords), _ptr(self.ind), \
-            _ptr(self.cnt), _ptr(self.grid)
-        a.devox, a.desc = _ptr(self.devox), _ptr(self.desc)
-        a.dinds[0], a.dinds[1] = _ptr(self.dinds), _ptr(s1.dinds)
-        a.dwgts[0], a.dwgts[1] = _ptr(self.dwgts), _ptr(s1.dwgts)
-        a.knn_ws[0], a.knn_ws[1] = _ptr(self.knn_ws), _ptr(s1.knn_ws)
-        a.knn_ws_bytes = self.knn_ws.numel()
-        a.vox_ws[0], a.vox_ws[1] = _ptr(self.ws), _ptr(s1.ws)
-        a.vox_ws_bytes = self.ws.numel()
-        if getattr(self, "_ws3", None) is None:
-            # the third voxel workspace of runner schedule 7
+        s1 = self._set(1)
+        if self._ws3 is None:
             self._ws3 = torch.empty_like(self.ws)
             self._order_new_buffers()
-        a.vox_ws3 = _ptr(self._ws3)
+        a.knn_ws[0], a.knn_ws[1] = _ptr(self.knn_ws), _ptr(s1.knn_ws)
+        a.knn_ws_bytes = self.knn_ws.numel()
+        a.vox_ws[0], a.vox_ws[1], a.vox_ws[2] = _ptr(self.ws), _ptr(s1.ws), _ptr(self._ws3)
+        a.vox_ws_bytes = self.ws.numel()
         a.devox_in_means = 0 if self.stream_devox else 1
         if match is not None:
             if 2 * match.pairs != self.b or match.n != self.n:
                 raise RuntimeError("match buffers are for %d pairs of %d points"
                                    % (match.pairs, match.n))
             a.match_pairs = match.pairs
-            a.corr12, a.corr21 = _ptr(match.corr12), _ptr(match.corr21)
-            a.idx1, a.idx2, a.match_count = _ptr(match.idx1), _ptr(match.idx2), \
-                _ptr(match.count)
             a.match_ws, a.match_ws_bytes = _ptr(match.ws), match.ws.numel()
+        names = [t[0] for t in self._step_outputs(self.knn_dist is not None, a.match_pairs)]
+        sets = (_lib.ExtractorSet * len(steps_io))()
+        for st, ((xyz, nrm, feat), o) in zip(sets, steps_io):
+            st.xyz, st.normals, st.features = _ptr(xyz), _ptr(nrm), _ptr(feat)
+            for f in names:
+                setattr(st, "match_count" if f == "count" else f, _ptr(o[f]))
+        a.nsets, a.sets = len(sets), sets  # a keeps sets alive
         return a
 
     def run_native(self, xyz, normals, features, steps, desc_steps=None, schedule=0,
                    timed=False, match=None):
-        """`steps` steps over the extractor's single buffer set, enqueued by
-        the library's native runner (pcr_extractor_run schedule 0: sort +
-        selection + PPF on s_nbr, prep + the fused grid kernel on s_vox).
-        One ctypes call for all steps.  The pipelined schedules 6 / 7 need
-        distinct output sets per step: run_ring.  timed: only schedules 6 /
-        7 bracket grid-stream kernels (grid_kernel_times()).  match: a
-        registration.PairMatch whose buffers receive, every step, the
-        mutual-NN matching of clouds [0, B/2) against [B/2, B)."""
+        """`steps` steps over one batch into the extractor's own buffers,
+        enqueued by the library's native runner (pcr_extractor_run over one
+        set, schedule 0: sort + selection + PPF on s_nbr, prep + the fused
+        grid kernel on s_vox).  One ctypes call for all steps.  The
+        pipelined schedules 6 / 7 need distinct output sets per step:
+        run_ring.  timed: only schedules 6 / 7 bracket grid-stream kernels
+        (grid_kernel_times()).  match: a registration.PairMatch whose
+        buffers receive, every step, the mutual-NN matching of clouds
+        [0, B/2) against [B/2, B)."""
         self._check_inputs(xyz, normals, features)
         # the argument block is built once per (inputs, match) and reused:
         # every other pointer is an extractor buffer, fixed for its life
         key = (xyz.data_ptr(), normals.data_ptr(), features.data_ptr(), match)
         if self._args_key != key:
-            self._args = self._make_args(xyz, normals, features, match)
+            own = {t[0]: getattr(self, t[0])
+                   for t in self._step_outputs(self.knn_dist is not None)}
+            if match is not None:
+                own.update(match.outputs())
+            self._args = self._make_args([((xyz, normals, features), own)], match)
             self._args_key = key
         self._run(steps, schedule, desc_steps, timed)
         return self.outputs(slot=0)
@@ -638,26 +648,12 @@ class SphExtractor:
         slot (knn_idx, local_ppf, norm_coords, ind, cnt, grid, devox, desc,
         dinds, dwgts; the matching outputs when match_pairs > 0), made once
         per ring size on the caller's stream."""
-        ring = getattr(self, "_ring", None)
+        ring = self._ring
         if ring is not None and len(ring) == nsets and self._ring_match == match_pairs:
             return ring
-        b, n, c, k, r3 = self.b, self.n, self.c, self.k, self.r ** 3
-        e, dev = torch.empty, self.device
-        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
-        ring = []
-        for _ in range(nsets):
-            o = {"knn_idx": e((b, k, n), **i32), "local_ppf": e((b, 4, k, n), **f32),
-                 "norm_coords": e((b, 3, n), **f32), "ind": e((b, n), **i32),
-                 "cnt": e((b, r3), **i32), "grid": e((b, c, r3), **f32),
-                 "devox": e((b, c, n), **f32), "desc": e((b, c), **f32),
-                 "dinds": e((b, 8, n), **i32), "dwgts": e((b, 8, n), **f32)}
-            if self.knn_dist is not None:
-                o["knn_dist"] = e((b, k, n), **f32)
-            if match_pairs:
-                for key in ("corr12", "corr21", "idx1", "idx2"):
-                    o[key] = e((match_pairs, n), **i32)
-                o["count"] = e((match_pairs,), **i32)
-            ring.append(o)
+        table = self._step_outputs(self.knn_dist is not None, match_pairs)
+        ring = [{name: torch.empty(shape, dtype=dtype, device=self.device)
+                 for name, shape, dtype in table} for _ in range(nsets)]
         self._ring, self._ring_match = ring, match_pairs
         self._order_new_buffers()
         return ring
@@ -665,7 +661,7 @@ class SphExtractor:
     def run_ring(self, batches, steps, set0=0, desc_steps=None, schedule=6, timed=False,
                  match=None):
         """`steps` pipelined steps of the native runner over a batch ring
-        (pcr_extractor_run with nsets = len(batches)): step s reads the
+        (pcr_extractor_run with one set per batch): step s reads the
         clouds of batches[(set0 + s) % R] = (xyz, normals, features) and
         writes every output into ring_outputs(R)[(set0 + s) % R], so with
         steps <= R each step's outputs survive the call and are readable on
@@ -700,18 +696,8 @@ class SphExtractor:
             key = ("ring", tuple(tuple(x.data_ptr() for x in t) for t in batches), match)
             self._ring_seen = (tuple(batches), match, key)
         if self._args_key != key:
-            a = self._make_args(*batches[0], match)
-            sets = (_lib.ExtractorSet * R)()
-            for i, ((xyz, nrm, feat), o) in enumerate(zip(batches, ring)):
-                st = sets[i]
-                st.xyz, st.normals, st.features = _ptr(xyz), _ptr(nrm), _ptr(feat)
-                for f in ("knn_idx", "local_ppf", "norm_coords", "ind", "cnt", "grid", "devox",
-                          "desc", "dinds", "dwgts", "corr12", "corr21", "idx1", "idx2"):
-                    setattr(st, f, _ptr(o[f]) if f in o else None)
-                st.knn_dist = _ptr(o["knn_dist"]) if "knn_dist" in o else None
-                st.match_count = _ptr(o["count"]) if "count" in o else None
-            a.nsets, a.sets = R, sets
-            self._args, self._args_key, self._ring_sets = a, key, sets
+            self._args = self._make_args(list(zip(batches, ring)), match)
+            self._args_key = key
         self._args.set0 = int(set0) % R
         self._run(steps, schedule, desc_steps, timed)
         return ring

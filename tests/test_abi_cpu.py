@@ -111,3 +111,43 @@ def test_extractor_structs_match_header(tmp_path):
         want.append("%s size %d" % (cname, ctypes.sizeof(cls)))
         want += ["%s %s %d" % (cname, f[0], getattr(cls, f[0]).offset) for f in cls._fields_]
     assert [g for g in got if g] == want
+
+
+def test_extractor_run_requires_sets():
+    """pcr_extractor_run refuses a call without sets (nsets = 0, sets = NULL)
+    and a set without its grid, with PCR_ERR_INVALID and a message naming
+    the cause.  Every pointer is a dummy: the argument checks precede the
+    first HIP call, so nothing is dereferenced and no GPU is needed."""
+    import ctypes
+    from pcr_amd import _lib
+    lib = _lib.load()
+    dummy = 0x1000
+
+    def run(nsets, with_sets=True, without=None, schedule=0):
+        a = _lib.ExtractorArgs()
+        a.b, a.n, a.c, a.k, a.r, a.relative = 2, 300, 5, 16, 16, 1
+        for q in range(2):
+            a.knn_ws[q] = dummy
+        for q in range(3):
+            a.vox_ws[q] = dummy
+        a.knn_ws_bytes = a.vox_ws_bytes = 1 << 20
+        sets = (_lib.ExtractorSet * 3)()
+        for st in sets:
+            for f, _ in _lib.ExtractorSet._fields_:
+                setattr(st, f, None if f == without else dummy)
+        a.nsets, a.set0 = nsets, 0
+        if with_sets:
+            a.sets = sets
+        rc = lib.pcr_extractor_run(None, ctypes.byref(a), 2, schedule, None, dummy, dummy, dummy,
+                                   dummy)
+        return rc, lib.pcr_last_error().decode()
+
+    for schedule in (0, 6, 7):
+        rc, msg = run(0, schedule=schedule)
+        assert rc == -1 and "sets" in msg, (schedule, msg)
+        rc, msg = run(3, with_sets=False, schedule=schedule)
+        assert rc == -1 and "sets" in msg, (schedule, msg)
+        rc, msg = run(3, without="grid", schedule=schedule)
+        assert rc == -1 and "set 0 incomplete" in msg and "grid" in msg, (schedule, msg)
+    rc, msg = run(-1)
+    assert rc == -1 and "sets" in msg, msg

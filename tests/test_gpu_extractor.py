@@ -73,9 +73,10 @@ def poison(ex):
 
 
 def test_extractor_native_runner(dev):
-    """pcr_extractor_run schedule 0 over the single buffer set (the native
-    multi-step enqueue): every step's descriptor and the final outputs equal
-    the single-step results; the removed schedules 1-5 are refused."""
+    """pcr_extractor_run schedule 0 over one set, the extractor's own buffers
+    (run_native, the native multi-step enqueue): every step's descriptor and
+    the final outputs equal the single-step results; the removed schedules
+    1-5 are refused."""
     schedule = 0
     from pcr_amd.extractor import SphExtractor
     b, n, c, k, r = 8, 1024, 64, 32, 32
@@ -118,6 +119,88 @@ def _ring_case(b, n, c, k, r):
         batches = [gaussian_clouds(b, n, seed=80 + i, c=c) for i in range(3)]
         _ring_exp[key] = (batches, [expected_step(*bt, k, r) for bt in batches])
     return _ring_exp[key]
+
+
+_STEP_KEYS = ("knn_dist", "knn_idx", "ind", "cnt", "grid", "devox", "dinds", "dwgts",
+              "norm_coords")
+_SMALL = (2, 300, 5, 16, 16)  # 16^3 voxels: the smallest grid the stream kernel takes; a
+#                               cloud below one prep workgroup and one 64-point block
+
+
+def _poison(tensors):
+    for t in tensors:
+        t.view(-1).view(torch.uint8).fill_(0xFF)
+
+
+def _assert_step(out, exp, tag):
+    """Every per-step output in `out` but the descriptor equals the oracle's."""
+    for key in _STEP_KEYS:
+        if key in out:
+            assert np.array_equal(N(out[key]), exp[key]), (tag, key)
+    assert np.array_equal(N(out["local_ppf"]), exp["local_ppf"], equal_nan=True), tag
+
+
+def test_extractor_native_runner_knn_dist(dev):
+    """run_native with distances wanted (with_dist=True), schedule 0, two
+    steps over poisoned buffers: knn_dist and every other output equal the
+    oracle, each step's descriptor too, and the returned tensors are the
+    extractor's own."""
+    from pcr_amd.extractor import SphExtractor
+    b, n, c, k, r = _SMALL
+    batches, exp = _ring_case(*_SMALL)
+    tx, tn, tf = (T(a, dev) for a in batches[0])
+    ex = SphExtractor(b, n, c, k, r, device=dev, with_dist=True)
+    poison(ex)
+    _poison([ex.knn_dist])
+    desc_steps = torch.full((2, b, c), float("nan"), device=dev)
+    out = ex.run_native(tx, tn, tf, 2, desc_steps, schedule=0)
+    torch.cuda.synchronize()
+    for key in ("knn_idx", "local_ppf", "norm_coords", "ind", "cnt", "grid", "devox", "dinds",
+                "dwgts", "desc"):
+        assert out[key] is getattr(ex, key), key
+    _assert_step(dict(out, knn_dist=ex.knn_dist), exp[0], "native")
+    for s in range(2):
+        assert np.array_equal(N(desc_steps[s]), exp[0]["desc"]), s
+
+
+def test_extractor_native_and_ring_alternate(dev):
+    """One extractor alternating between run_native and run_ring over three
+    distinct batches A, B, C (the argument block is cached across both entry
+    points): run_native(A), run_ring([A, B], schedule 6), run_native(B),
+    run_ring([B, C], schedule 0), every call over poisoned buffers and
+    compared with the oracle of its batches."""
+    from pcr_amd.extractor import SphExtractor
+    b, n, c, k, r = _SMALL
+    batches, exp = _ring_case(*_SMALL)
+    tb = [tuple(T(a, dev) for a in bt) for bt in batches]
+    ex = SphExtractor(b, n, c, k, r, device=dev)
+    ring = ex.ring_outputs(2)
+
+    def native(i):
+        poison(ex)
+        desc_steps = torch.full((2, b, c), float("nan"), device=dev)
+        out = ex.run_native(*tb[i], 2, desc_steps, schedule=0)
+        torch.cuda.synchronize()
+        _assert_step(out, exp[i], ("native", i))
+        for s in range(2):
+            assert np.array_equal(N(desc_steps[s]), exp[i]["desc"]), ("native", i, s)
+
+    def ringed(ids, schedule):
+        poison(ex)
+        for o in ring:
+            _poison(o.values())
+        desc_steps = torch.full((2, b, c), float("nan"), device=dev)
+        got = ex.run_ring([tb[i] for i in ids], 2, 0, desc_steps, schedule=schedule)
+        torch.cuda.synchronize()
+        assert got is ring
+        for s, i in enumerate(ids):
+            _assert_step(ring[s], exp[i], ("ring", schedule, i))
+            assert np.array_equal(N(desc_steps[s]), exp[i]["desc"]), ("ring", schedule, i)
+
+    native(0)
+    ringed((0, 1), 6)
+    native(1)
+    ringed((1, 2), 0)
 
 
 def _check_batch_ring(dev, schedule, shape, stream_devox, with_dist):
@@ -201,7 +284,7 @@ def test_extractor_runner_multi_queue_rings(dev, schedule, rings):
     KNN queue) over rings that one call wraps: a ring size that is a
     multiple of the voxel queue count rewrites each set on its own queue (no
     ring events: 2 sets x 5 steps, 3 x 7), another size on another queue
-    behind the per-set event (5 x 7, 4 x 9).  The single-set runner refuses
+    behind the per-set event (5 x 7, 4 x 9).  run_native (one set) refuses
     both, and a ring smaller than the voxel queue count is refused."""
     from pcr_amd.extractor import SphExtractor
     b, n, c, k, r = 4, 1024, 16, 32, 32
