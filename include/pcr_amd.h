@@ -403,6 +403,50 @@ pcr_status pcr_icp_point_to_point(const float *xyz1, const float *xyz2, int p, i
                                   int *corr, int *num_corr, double *fitness, double *rmse,
                                   int *iterations, int *status, void *stream);
 
+/* ------------------------------- Fast Global Registration -----------------
+ * utils/open3d_func.py:34-75 (register_one_pair with func='fgr': Open3D
+ * registration_fast_based_on_feature_matching), for p pairs, from the
+ * matching's correspondences (the scalar math is
+ * include/pcr_fgr.h and the sampler and edge check of include/pcr_rigid.h).
+ *   xyz1 [p,3,n1], xyz2 [p,3,n2]; idx1 / idx2 [p,n1] and count [p] as for
+ *   pcr_rigid_ransac: M = count[q] clamped to [0, n1] slots.
+ *   Tuple test: max_tuples = 0: the list L is the slots 0 .. M-1.  Else
+ *   H = trials_per_corr * M trials (none when M < 3); trial h takes the three
+ *   slots pcr_rigid_triple draws from (seed, q, h, M) and is accepted iff
+ *   pcr_rigid_edge_ok holds at tuple_scale; the first max_tuples accepted trials
+ *   in ascending h count, L is their slots in that order (three per trial,
+ *   duplicates kept); num_trials = the last counted h + 1 when the cap was
+ *   reached, else H (0 with max_tuples = 0).  K = |L|.
+ *   K < 10: status 1.  Else the clouds' fp64 centroids m1 / m2 (over all their
+ *   points, in the summation order of pcr_fgr_sum) and s = the largest
+ *   distance of a point to its cloud's centroid; s zero or not finite:
+ *   status 2.  d = s, mu = 1 (absolute_scale: d = 1, mu = s); L's points in
+ *   units of d about the centroids.
+ *   Loop, `iterations` times from T = identity: the moved target points, the
+ *   weights (mu / (|r|^2 + mu))^2, the 6 x 6 normal equations of
+ *   J = [[q]x, -I], their fp64 Cholesky solve (a pivot not finite and
+ *   positive: status 3, T as reached so far), T <- Delta T with
+ *   Delta = [Rz Ry Rx, translation]; then, with decrease_mu, every fourth
+ *   iteration (it % 4 == 0) while mu > max_corr_dist (compared in normalised
+ *   units, unscaled, as Open3D does): mu /= division_factor.
+ *   transform [p,4,4] fp64: the inverse of T in original units, xyz2 ~ R xyz1
+ *   + t, bottom row 0 0 0 1 (status 1 / 2: the identity, mu 0); slots
+ *   [p, kcap], kcap = 3 * max_tuples (max_tuples = 0: n1): L, then -1;
+ *   num_corr [p] = K; num_trials [p]; mu [p] fp64: the final value;
+ *   status [p].  0 <= iterations <= 100000; division_factor > 1;
+ *   0 <= tuple_scale < 1; max_tuples >= 0; trials_per_corr >= 0 and
+ *   trials_per_corr * n1 <= 2^31 - 1; max_corr_dist >= 0.  A bad pair (NaN,
+ *   degenerate) never fails the call and touches no other pair.
+ * Bit-identical from run to run.  Runs on `stream`; the workspace
+ * (pcr_fgr_workspace_size bytes: L's point pairs) is the caller's. */
+size_t pcr_fgr_workspace_size(int p, int n1, int max_tuples);
+pcr_status pcr_fgr(const float *xyz1, const float *xyz2, int p, int n1, int n2, const int *idx1,
+                   const int *idx2, const int *count, double max_corr_dist, int iterations,
+                   double division_factor, int decrease_mu, float tuple_scale, int max_tuples,
+                   int trials_per_corr, int absolute_scale, unsigned seed, double *transform,
+                   int *slots, int *num_corr, int *num_trials, double *mu, int *status,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------ LRF change_coords (8f f2) ----------
  * models/pvcnn_classify.py:153-184 (rot_invariant_preprocess ==
  * 'change_coords'), one cloud per workgroup, no host round trip.

@@ -25,6 +25,7 @@
 //     n1 keeps the nearest index in corr and re-reads the points.
 #include "common.hpp"
 #include "pcr_rigid.h"
+#include "rigid_pair.hpp"
 
 // launch shape; other shapes for A/B builds (make ab DEFS=-DPCR_ICP_THREADS=256
 // -DPCR_ICP_PPT=4)
@@ -49,28 +50,6 @@ static_assert(kIT % kWave == 0 && kIT <= 1024 && kIChunk % kIPad == 0, "icp laun
 inline int icp_cap(int n2) { return min((n2 + kIPad - 1) / kIPad * kIPad, kIChunk); }
 inline size_t icp_lds_bytes(int cap) {
   return (size_t)cap * 12 + (size_t)kIW * 16 * sizeof(double) + 16 * sizeof(double);
-}
-
-// Sum of v[0..N) over the workgroup, the same bits in every thread
-// (rigid_block_sum for kIW waves).
-template <int N>
-__device__ inline void icp_block_sum(double (&v)[N], double (*red_s)[16]) {
-  static_assert(N <= 16, "row of red_s");
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < N; i++) v[i] = wave_sum_d(v[i]);
-  if ((tid & (kWave - 1)) == 0) {
-#pragma unroll
-    for (int i = 0; i < N; i++) red_s[tid >> 6][i] = v[i];
-  }
-  lds_barrier();
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double s = red_s[0][i];
-    for (int w = 1; w < kIW; w++) s += red_s[w][i];
-    v[i] = s;
-  }
-  lds_barrier();
 }
 
 // targets [c0, c0 + len) of the pair -> the three LDS planes, NaN up to the
@@ -203,7 +182,7 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
         if (!kResident && i < n1) cq[i] = bj[k];
       }
     }
-    icp_block_sum(acc, red_s);
+    block_sum_d<kIW>(acc, red_s);
     M = acc[0];
     E = acc[1];
     const double fit = M / (double)n1;
@@ -254,7 +233,7 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
         }
       }
     }
-    icp_block_sum(cov, red_s);
+    block_sum_d<kIW>(cov, red_s);
     if (tid < kWave) {
       pcr_rigid_from_cov(ca, cb, cov, R, t);
       if (tid == 0) {

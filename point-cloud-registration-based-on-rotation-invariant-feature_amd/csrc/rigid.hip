@@ -22,52 +22,13 @@
 //     run), then the mask and count under the final transform.
 #include "common.hpp"
 #include "pcr_rigid.h"
+#include "rigid_pair.hpp"
 
 namespace pcr {
 
 constexpr int kRB = 256;       // threads = hypotheses per workgroup
 constexpr int kRChunk = 1024;  // correspondence slots per LDS chunk (6 floats each: 24 KB)
 constexpr int kRW = kRB / kWave;
-
-struct RigidPair {
-  const float *a, *b;  // the pair's clouds, [3][n1] / [3][n2]
-  const int *i1, *i2;  // its correspondence rows
-  int n1, n2, m;       // m: valid slots
-};
-
-__device__ inline RigidPair rigid_pair(const float* xyz1, const float* xyz2, int n1, int n2,
-                                       const int* idx1, const int* idx2, const int* count,
-                                       int q) {
-  RigidPair pr;
-  pr.a = xyz1 + (size_t)q * 3 * n1;
-  pr.b = xyz2 + (size_t)q * 3 * n2;
-  pr.i1 = idx1 + (size_t)q * n1;
-  pr.i2 = idx2 + (size_t)q * n1;
-  pr.n1 = n1;
-  pr.n2 = n2;
-  pr.m = min(max(count[q], 0), n1);
-  return pr;
-}
-
-// slot s < m -> its source and target point; indices are clamped into the
-// clouds, so a malformed correspondence row cannot read out of bounds
-__device__ inline void rigid_slot(const RigidPair& pr, int s, float* a, float* b) {
-  const int ia = min(max(pr.i1[s], 0), pr.n1 - 1);
-  const int ib = min(max(pr.i2[s], 0), pr.n2 - 1);
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    a[d] = pr.a[(size_t)d * pr.n1 + ia];
-    b[d] = pr.b[(size_t)d * pr.n2 + ib];
-  }
-}
-
-__device__ inline void rigid_triple_points(const RigidPair& pr, unsigned seed, int q, int h,
-                                           float (&a)[9], float (&b)[9]) {
-  int sl[3];
-  pcr_rigid_triple(seed, (unsigned)q, (unsigned)h, (unsigned)pr.m, sl);
-#pragma unroll
-  for (int k = 0; k < 3; k++) rigid_slot(pr, sl[k], a + 3 * k, b + 3 * k);
-}
 
 // block result key: larger is better -- score first, then the lower h; 0: none
 __device__ inline unsigned long long rigid_key(int score, int h) {
@@ -173,27 +134,6 @@ __global__ __launch_bounds__(kRB) void rigid_hyp_kernel(
   }
 }
 
-// Sum of v[0..N) over the workgroup, the same bits in every thread: the
-// butterfly over the wave, then the waves in order.
-template <int N>
-__device__ inline void rigid_block_sum(double (&v)[N], double (*red_s)[16]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < N; i++) v[i] = wave_sum_d(v[i]);
-  if ((tid & (kWave - 1)) == 0) {
-#pragma unroll
-    for (int i = 0; i < N; i++) red_s[tid >> 6][i] = v[i];
-  }
-  lds_barrier();
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double s = red_s[0][i];
-    for (int w = 1; w < kRW; w++) s += red_s[w][i];
-    v[i] = s;
-  }
-  lds_barrier();
-}
-
 __global__ __launch_bounds__(kRB) void rigid_refit_kernel(
     const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n1, int n2,
     const int* __restrict__ idx1, const int* __restrict__ idx2, const int* __restrict__ count,
@@ -254,7 +194,7 @@ __global__ __launch_bounds__(kRB) void rigid_refit_kernel(
         }
       }
     }
-    rigid_block_sum(acc, red_s);
+    block_sum_d<kRW>(acc, red_s);
     if (acc[0] < 3.0) break;  // uniform
     double ca[3], cb[3], cov[9];
 #pragma unroll
@@ -275,7 +215,7 @@ __global__ __launch_bounds__(kRB) void rigid_refit_kernel(
             cov[3 * i + j] += ((double)a[i] - ca[i]) * ((double)b[j] - cb[j]);
       }
     }
-    rigid_block_sum(cov, red_s);
+    block_sum_d<kRW>(cov, red_s);
     pcr_rigid_from_cov(ca, cb, cov, R, t);
     pcr_rigid_round(R, t, T);
   }

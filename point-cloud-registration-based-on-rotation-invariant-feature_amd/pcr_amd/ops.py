@@ -595,3 +595,53 @@ def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, re
         float(rel_fitness), float(rel_rmse), _ptr(transform), _ptr(corr), _ptr(num_corr),
         _ptr(fitness), _ptr(rmse), _ptr(iterations), _ptr(status), _stream()), "icp")
     return transform, corr, num_corr, fitness, rmse, iterations, status
+
+
+def fgr(xyz1, xyz2, idx1, idx2, count, max_corr_dist=0.08, iterations=64, division_factor=1.4,
+        decrease_mu=True, tuple_scale=0.95, max_tuples=1000, trials_per_corr=100,
+        absolute_scale=False, seed=0, workspace=None):
+    """Fast Global Registration of p registration pairs from their
+    correspondences (utils/open3d_func.py:34-75, register_one_pair(func='fgr'),
+    batched; the defaults are Open3D's FastGlobalRegistrationOption with the
+    reference's maximum_correspondence_distance 0.08): xyz1 [p, 3, n1], xyz2
+    [p, 3, n2], idx1 / idx2 [p, n1] and count [p] as mutual_nn_match returns
+    them -> (transform [p, 4, 4] fp64 with xyz2 ~ R xyz1 + t, slots
+    [p, 3 * max_tuples] -- the correspondence slots the tuple test kept, three
+    per accepted triple in trial order, then -1 ([p, n1] and the slots
+    themselves with max_tuples = 0) --, num_corr [p] their number, num_trials
+    [p], mu [p] fp64 the final line-process parameter, status [p]: 0 ok, 1
+    fewer than 10 correspondences kept, 2 degenerate or non-finite clouds, 3 a
+    singular step).  Seeded and bit-identical from run to run."""
+    _check(xyz1, "xyz1")
+    _check(xyz2, "xyz2")
+    _check(idx1, "idx1", "int")
+    _check(idx2, "idx2", "int")
+    _check(count, "count", "int")
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
+            xyz1.shape[0] != xyz2.shape[0]:
+        raise RuntimeError("fgr: expected [p, 3, n] clouds with equal pair counts")
+    p, _, n1 = xyz1.shape
+    n2 = xyz2.shape[2]
+    if tuple(idx1.shape) != (p, n1) or tuple(idx2.shape) != (p, n1) or tuple(count.shape) != (p,):
+        raise RuntimeError("fgr: expected idx1 / idx2 [p, n1] and count [p]")
+    max_tuples = int(max_tuples)
+    if max_tuples < 0:
+        raise RuntimeError("fgr: negative max_tuples (%d)" % max_tuples)
+    dev = xyz1.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    transform = torch.empty((p, 4, 4), **f64)
+    slots = torch.empty((p, 3 * max_tuples if max_tuples else n1), **i32)
+    num_corr, num_trials, status = (torch.empty((p,), **i32) for _ in range(3))
+    mu = torch.empty((p,), **f64)
+    lib = _lib.load()
+    need = max(256, lib.pcr_fgr_workspace_size(p, n1, max_tuples))
+    ws = workspace if workspace is not None and workspace.numel() >= need else \
+        torch.empty(need, dtype=torch.uint8, device=dev)
+    _lib.check(lib.pcr_fgr(
+        _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(idx1), _ptr(idx2), _ptr(count),
+        float(max_corr_dist), int(iterations), float(division_factor), int(bool(decrease_mu)),
+        float(tuple_scale), max_tuples, int(trials_per_corr), int(bool(absolute_scale)),
+        int(seed) & 0xFFFFFFFF, _ptr(transform), _ptr(slots), _ptr(num_corr), _ptr(num_trials),
+        _ptr(mu), _ptr(status), _ptr(ws), ws.numel(), _stream()), "fgr")
+    return transform, slots, num_corr, num_trials, mu, status

@@ -22,7 +22,9 @@ PairExtractor.register, or register_pairs for features from elsewhere;
 rre_rte and alignment_rmse are the reference's error meters.  ops.icp (the
 reference's func='icp' solver) re-fits a transform over every
 point within a distance: icp_pairs on its own, or `icp=` of register /
-register_pairs as the refinement of the RANSAC estimate.
+register_pairs as the refinement of the RANSAC estimate.  ops.fgr (the
+reference's func='fgr' solver) is the other estimate from the
+correspondences: fgr_pairs, or solver="fgr" of register / register_pairs.
 
 The native runner (pcr_extractor_run with match_pairs = P) enqueues the
 matching on each step's voxel queue right after its devox (behind the grid
@@ -106,16 +108,21 @@ class PairExtractor:
     def reserve_timing(self, timed_steps):
         self.ex.reserve_timing(timed_steps)
 
-    def register(self, xyz, normals, features, icp=None, **ransac):
+    def register(self, xyz, normals, features, icp=None, solver="ransac", **ransac):
         """forward, then the rigid transform of every pair from its
         correspondences (ops.rigid_ransac on the current stream; `ransac`:
         its keyword arguments): forward's keys plus transform [P, 4, 4] fp64
         (target ~ R source + t), inliers, num_inliers, best_hyp and
         reg_status.  icp: a dict of ops.icp keywords (may be empty) refines
         that transform by point-to-point ICP into the icp_* keys of
-        register_pairs."""
+        register_pairs.  solver="fgr": ops.fgr instead (the keywords are
+        its own), with the keys of fgr_pairs."""
         out = self.forward(xyz, normals, features)
         p = self.pairs
+        if _solver(solver) == "fgr":
+            out.update(_fgr_solve(xyz[:p], xyz[p:], out["idx1"], out["idx2"], out["count"], icp,
+                                  ransac))
+            return out
         got = ops.rigid_ransac(xyz[:p], xyz[p:], out["idx1"], out["idx2"], out["count"], **ransac)
         out.update(zip(("transform", "inliers", "num_inliers", "best_hyp", "reg_status"), got))
         if icp is not None:
@@ -141,7 +148,39 @@ def _icp_refine(xyz1, xyz2, transform, icp):
     return {"icp_" + k: v for k, v in zip(ICP_KEYS, got)}
 
 
-def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **ransac):
+FGR_KEYS = ("transform", "slots", "num_corr", "num_trials", "mu", "reg_status")
+
+
+def _solver(solver):
+    if solver not in ("ransac", "fgr"):
+        raise RuntimeError("unknown solver %r: expected 'ransac' or 'fgr'" % (solver,))
+    return solver
+
+
+def _fgr_solve(xyz1, xyz2, idx1, idx2, count, icp, fgr):
+    """ops.fgr on a matching's output -> the FGR_KEYS, plus the icp_* keys"""
+    out = dict(zip(FGR_KEYS, ops.fgr(xyz1, xyz2, idx1, idx2, count, **fgr)))
+    if icp is not None:
+        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp))
+    return out
+
+
+def fgr_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **fgr):
+    """register_one_pair(func='fgr') (utils/open3d_func.py:34-75) after
+    find_correspondence_one_pair, batched and on the device: the arguments of
+    register_pairs -> a dict with the matching (idx1, idx2, count) and
+    ops.fgr's outputs (transform, slots, num_corr, num_trials, mu,
+    reg_status); `fgr`: its keyword arguments.  icp: a dict of ops.icp keywords
+    (may be empty) refines the transform into the icp_* keys, as in
+    register_pairs."""
+    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
+    out = {"idx1": idx1, "idx2": idx2, "count": count}
+    out.update(_fgr_solve(xyz1, xyz2, idx1, idx2, count, icp, fgr))
+    return out
+
+
+def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, solver="ransac",
+                   **ransac):
     """Pair in, transform out (datasets/deepgmr_mn40.py:165-244,
     find_correspondence_one_pair + register_one_pair(func='ransac'), batched
     and on the device): xyz1 [p, 3, n1], xyz2 [p, 3, n2] and per-point
@@ -152,7 +191,10 @@ def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **ra
     keywords (may be empty) refines the RANSAC transform by point-to-point
     ICP over every point; its outputs come as icp_transform, icp_corr,
     icp_num_corr, icp_fitness, icp_rmse, icp_iterations and icp_status, the
-    other keys are unchanged."""
+    other keys are unchanged.  solver="fgr": fgr_pairs with the same
+    arguments (the keywords are ops.fgr's)."""
+    if _solver(solver) == "fgr":
+        return fgr_pairs(xyz1, xyz2, feat1, feat2, channel_major=channel_major, icp=icp, **ransac)
     _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
     got = ops.rigid_ransac(xyz1, xyz2, idx1, idx2, count, **ransac)
     out = {"idx1": idx1, "idx2": idx2, "count": count}
