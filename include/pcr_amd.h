@@ -447,6 +447,55 @@ pcr_status pcr_fgr(const float *xyz1, const float *xyz2, int p, int n1, int n2, 
                    int *slots, int *num_corr, int *num_trials, double *mu, int *status,
                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------- TEASER-style robust registration ---------
+ * datasets/modelnet40_registration.py:274-327 (register_one_pair with
+ * func='teaserpp': TEASER++ with GNC-TLS at noise_bound 0.02, cbar2 1), for p
+ * pairs, from the matching's correspondences, with a bounded greedy clique
+ * search in place of TEASER++'s exact one (the scalar math is
+ * include/pcr_teaser.h and the edge length and rotation solve of
+ * include/pcr_rigid.h).
+ *   xyz1 [p,3,n1], xyz2 [p,3,n2]; idx1 / idx2 [p,n1] and count [p] as for
+ *   pcr_fgr: M = count[q] clamped to [0, n1] slots, slot s pairs a_s with b_s.
+ *   beta = 2 noise_bound sqrt(cbar2), rho = noise_bound sqrt(cbar2) (fp64, host).
+ *   Graph: slots i != j are joined iff | |a_j - a_i| - |b_j - b_i| | <= beta
+ *   (pcr_teaser_edge: fp64 lengths of the fp32 points; a NaN never joins).
+ *   Clique: the slots ranked by degree, descending, lowest slot first; seed r <
+ *   S is the slot of rank r, S = M (seeds = 0) or min(seeds, M).  From a seed v:
+ *   C = {v}, P = N(v); while P is not empty its best-ranked member u joins C and
+ *   P <- P & N(u).  The largest C wins, the best-ranked seed on ties.
+ *   inlier_selection = 0: C is all M slots.  K = |C|; K < 3: status 1.
+ *   Rotation: GNC-TLS over the K (K - 1) / 2 TIMs u = a_j - a_i, v = b_j - b_i
+ *   (i < j in C), nu^2 = beta^2, weights 1 at first; at most max_iters times:
+ *   H = sum w u v^T, R from H (pcr_teaser_rotation), r^2 = |v - R u|^2; in the
+ *   first iteration mu from max r^2 (pcr_teaser_mu0; max r^2 not finite: status
+ *   2; mu <= 0 or not finite: done); cost = sum w r^2, the new w from r^2 and mu
+ *   (pcr_teaser_weight), mu *= gnc_factor; done when |cost - previous cost| <
+ *   cost_threshold.
+ *   Status 3: the iteration limit (R is reported).
+ *   Translation, per axis: X_k = b_k - (R a_k); over the midpoints of the 2 K
+ *   endpoints X_k -+ rho sorted by value, then number (pcr_teaser_vote_at): the
+ *   mean of {k : |X_k - m| <= rho} with the lowest sum_k min((X_k - mean)^2,
+ *   rho^2), the earliest midpoint on ties.  Slot k of C is an inlier iff
+ *   |X_k - t| <= rho on all three axes.
+ *   transform [p,4,4] fp64, xyz2 ~ R xyz1 + t, bottom row 0 0 0 1 (status 1 / 2:
+ *   the identity, no inliers); clique [p,n1]: C as ascending slots, then -1;
+ *   clique_size [p] = K; inliers [p,n1]: 0 / 1 per slot; num_inliers [p];
+ *   iterations [p]: rotation solves made (0 with status 1); status [p].
+ *   n1 <= 4096; noise_bound, cbar2 > 0; gnc_factor > 1; 1 <= max_iters <= 1000;
+ *   cost_threshold >= 0; seeds >= 0.  A bad pair (NaN, M < 3, coincident
+ *   points) never fails the call and touches no other pair.
+ * Bit-identical from run to run and alone or inside a batch.  Runs on
+ * `stream`; the workspace (pcr_teaser_workspace_size bytes: per pair the bit
+ * rows, n1 * ceil(n1 / 64) * 8 bytes, and two ints per slot; the total rounded
+ * up to 256) is the caller's. */
+size_t pcr_teaser_workspace_size(int p, int n1);
+pcr_status pcr_teaser(const float *xyz1, const float *xyz2, int p, int n1, int n2, const int *idx1,
+                      const int *idx2, const int *count, double noise_bound, double cbar2,
+                      double gnc_factor, int max_iters, double cost_threshold, int seeds,
+                      int inlier_selection, double *transform, int *clique, int *clique_size,
+                      int *inliers, int *num_inliers, int *iterations, int *status,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------ LRF change_coords (8f f2) ----------
  * models/pvcnn_classify.py:153-184 (rot_invariant_preprocess ==
  * 'change_coords'), one cloud per workgroup, no host round trip.

@@ -645,3 +645,48 @@ def fgr(xyz1, xyz2, idx1, idx2, count, max_corr_dist=0.08, iterations=64, divisi
         int(seed) & 0xFFFFFFFF, _ptr(transform), _ptr(slots), _ptr(num_corr), _ptr(num_trials),
         _ptr(mu), _ptr(status), _ptr(ws), ws.numel(), _stream()), "fgr")
     return transform, slots, num_corr, num_trials, mu, status
+
+
+def teaser(xyz1, xyz2, idx1, idx2, count, noise_bound=0.02, cbar2=1.0, gnc_factor=1.4,
+           max_iters=100, cost_threshold=1e-12, seeds=0, inlier_selection=True, workspace=None):
+    """TEASER-style robust registration of p registration pairs from their
+    correspondences (datasets/modelnet40_registration.py:274-327,
+    register_one_pair(func='teaserpp'), batched; noise_bound and cbar2 are the
+    reference's call, the rest TEASER++'s defaults): xyz1
+    [p, 3, n1], xyz2 [p, 3, n2], idx1 / idx2 [p, n1] and count [p] as
+    mutual_nn_match returns them -> (transform [p, 4, 4] fp64 with xyz2 ~ R xyz1
+    + t, clique [p, n1] -- the slots of the pairwise-consistent set a bounded
+    greedy search found, ascending, then -1 (every slot with inlier_selection
+    off) --, clique_size [p], inliers [p, n1] 0 / 1 per slot, num_inliers [p],
+    iterations [p] the rotation solves made, status [p]: 0 ok, 1 a clique of
+    fewer than 3, 2 non-finite points, 3 the iteration limit).  seeds: how many
+    of the best-ranked slots start a search (0: all).  n1 <= 4096.
+    Bit-identical from run to run."""
+    _check(xyz1, "xyz1")
+    _check(xyz2, "xyz2")
+    _check(idx1, "idx1", "int")
+    _check(idx2, "idx2", "int")
+    _check(count, "count", "int")
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
+            xyz1.shape[0] != xyz2.shape[0]:
+        raise RuntimeError("teaser: expected [p, 3, n] clouds with equal pair counts")
+    p, _, n1 = xyz1.shape
+    n2 = xyz2.shape[2]
+    if tuple(idx1.shape) != (p, n1) or tuple(idx2.shape) != (p, n1) or tuple(count.shape) != (p,):
+        raise RuntimeError("teaser: expected idx1 / idx2 [p, n1] and count [p]")
+    dev = xyz1.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    transform = torch.empty((p, 4, 4), dtype=torch.float64, device=dev)
+    clique, inliers = torch.empty((p, n1), **i32), torch.empty((p, n1), **i32)
+    clique_size, num_inliers, iterations, status = (torch.empty((p,), **i32) for _ in range(4))
+    lib = _lib.load()
+    need = max(256, lib.pcr_teaser_workspace_size(p, n1))
+    ws = workspace if workspace is not None and workspace.numel() >= need else \
+        torch.empty(need, dtype=torch.uint8, device=dev)
+    _lib.check(lib.pcr_teaser(
+        _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(idx1), _ptr(idx2), _ptr(count), float(noise_bound),
+        float(cbar2), float(gnc_factor), int(max_iters), float(cost_threshold), int(seeds),
+        int(bool(inlier_selection)), _ptr(transform), _ptr(clique), _ptr(clique_size),
+        _ptr(inliers), _ptr(num_inliers), _ptr(iterations), _ptr(status), _ptr(ws), ws.numel(),
+        _stream()), "teaser")
+    return transform, clique, clique_size, inliers, num_inliers, iterations, status

@@ -25,6 +25,9 @@ point within a distance: icp_pairs on its own, or `icp=` of register /
 register_pairs as the refinement of the RANSAC estimate.  ops.fgr (the
 reference's func='fgr' solver) is the other estimate from the
 correspondences: fgr_pairs, or solver="fgr" of register / register_pairs.
+ops.teaser (the reference's func='teaserpp' solver with a bounded clique
+search) is the one meant for mostly wrong matches:
+teaser_pairs, or solver="teaser".
 
 The native runner (pcr_extractor_run with match_pairs = P) enqueues the
 matching on each step's voxel queue right after its devox (behind the grid
@@ -116,12 +119,14 @@ class PairExtractor:
         reg_status.  icp: a dict of ops.icp keywords (may be empty) refines
         that transform by point-to-point ICP into the icp_* keys of
         register_pairs.  solver="fgr": ops.fgr instead (the keywords are
-        its own), with the keys of fgr_pairs."""
+        its own), with the keys of fgr_pairs; solver="teaser": ops.teaser,
+        with the keys of teaser_pairs."""
         out = self.forward(xyz, normals, features)
         p = self.pairs
-        if _solver(solver) == "fgr":
-            out.update(_fgr_solve(xyz[:p], xyz[p:], out["idx1"], out["idx2"], out["count"], icp,
-                                  ransac))
+        if _solver(solver) != "ransac":
+            solve = _fgr_solve if solver == "fgr" else _teaser_solve
+            out.update(solve(xyz[:p], xyz[p:], out["idx1"], out["idx2"], out["count"], icp,
+                             ransac))
             return out
         got = ops.rigid_ransac(xyz[:p], xyz[p:], out["idx1"], out["idx2"], out["count"], **ransac)
         out.update(zip(("transform", "inliers", "num_inliers", "best_hyp", "reg_status"), got))
@@ -152,8 +157,8 @@ FGR_KEYS = ("transform", "slots", "num_corr", "num_trials", "mu", "reg_status")
 
 
 def _solver(solver):
-    if solver not in ("ransac", "fgr"):
-        raise RuntimeError("unknown solver %r: expected 'ransac' or 'fgr'" % (solver,))
+    if solver not in ("ransac", "fgr", "teaser"):
+        raise RuntimeError("unknown solver %r: expected 'ransac', 'fgr' or 'teaser'" % (solver,))
     return solver
 
 
@@ -179,6 +184,33 @@ def fgr_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **fgr):
     return out
 
 
+TEASER_KEYS = ("transform", "clique", "clique_size", "inliers", "num_inliers", "iterations",
+               "reg_status")
+
+
+def _teaser_solve(xyz1, xyz2, idx1, idx2, count, icp, teaser):
+    """ops.teaser on a matching's output -> the TEASER_KEYS, plus the icp_* keys"""
+    out = dict(zip(TEASER_KEYS, ops.teaser(xyz1, xyz2, idx1, idx2, count, **teaser)))
+    if icp is not None:
+        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp))
+    return out
+
+
+def teaser_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **teaser):
+    """register_one_pair(func='teaserpp')
+    (datasets/modelnet40_registration.py:274-327) after
+    find_correspondence_one_pair, batched and on the device: the arguments of
+    register_pairs -> a dict with the matching (idx1, idx2, count) and
+    ops.teaser's outputs (transform, clique, clique_size, inliers, num_inliers,
+    iterations, reg_status); `teaser`: its keyword arguments.  icp: a dict of
+    ops.icp keywords (may be empty) refines the transform into the icp_* keys,
+    as in register_pairs."""
+    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
+    out = {"idx1": idx1, "idx2": idx2, "count": count}
+    out.update(_teaser_solve(xyz1, xyz2, idx1, idx2, count, icp, teaser))
+    return out
+
+
 def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, solver="ransac",
                    **ransac):
     """Pair in, transform out (datasets/deepgmr_mn40.py:165-244,
@@ -192,9 +224,11 @@ def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, solv
     ICP over every point; its outputs come as icp_transform, icp_corr,
     icp_num_corr, icp_fitness, icp_rmse, icp_iterations and icp_status, the
     other keys are unchanged.  solver="fgr": fgr_pairs with the same
-    arguments (the keywords are ops.fgr's)."""
-    if _solver(solver) == "fgr":
-        return fgr_pairs(xyz1, xyz2, feat1, feat2, channel_major=channel_major, icp=icp, **ransac)
+    arguments (the keywords are ops.fgr's); solver="teaser": teaser_pairs (the
+    keywords are ops.teaser's)."""
+    if _solver(solver) != "ransac":
+        pairs = fgr_pairs if solver == "fgr" else teaser_pairs
+        return pairs(xyz1, xyz2, feat1, feat2, channel_major=channel_major, icp=icp, **ransac)
     _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
     got = ops.rigid_ransac(xyz1, xyz2, idx1, idx2, count, **ransac)
     out = {"idx1": idx1, "idx2": idx2, "count": count}
