@@ -3,8 +3,12 @@
 //
 // knn_wsel_kernel (round 5): the self-KNN selection of clouds of <= 64 R
 // points, k <= 32, transposed -- one query per wave instruction, the cloud's
-// candidates in the lanes.  Lane l holds the Morton-sorted candidates
-// 64 r + l (r < R) in registers for the whole launch, so a query costs:
+// candidates in the lanes.  The workgroup lands the cloud's sorted x / y / z /
+// index rows in LDS once (LDS-DMA, 16 KB at 1024 points; until round 7 each
+// of its 8 or 12 waves loaded the whole cloud from global memory: 53 loads per
+// wave, 12x the vector-L1 requests).  Lane l then holds the Morton-sorted
+// candidates 64 r + l (r < R) in registers for the whole launch, filled from
+// LDS two registers per ds_read2st64_b32, so a query costs:
 //
 //  1. distances  its R distances per lane with the reference's FMA chain
 //                (knn.cu:20-23; two candidates per packed instruction);
@@ -13,9 +17,14 @@
 //                per-pair atomic and no histogram).  t starts from the
 //                previous query's threshold (Morton neighbours have similar
 //                k-th distances) and moves by count ~ t^1.5 interpolation,
-//                bracketed, until k <= count <= 64: 1.5 passes on average;
+//                bracketed, until k <= count <= 64: 1.78 passes on average
+//                with 12 waves taking a block's queries one at a time (a
+//                wave's previous query is ~12 Morton positions back; seeding
+//                from the nearest finished query of the block instead saves
+//                0.03 passes in scripts/wsel_seed_model.py: not built);
 //  3. compact    the <= 64 keys with d <= t into one lane each (ballot +
-//                mbcnt slots in the wave's LDS row);
+//                mbcnt slots in the wave's LDS rows; per candidate register
+//                4 VALU and one ds_write2st64_b32 of distance + position);
 //  4. sort       a 64-lane bitonic sort of 32-bit keys (d bits >> 5 << 6 |
 //                slot): DPP / swizzle partners, min / max / select per stage.
 //                Two keys whose truncated distances tie inside the first k
@@ -34,15 +43,6 @@
 
 namespace pcr {
 
-// v, opaque to the optimiser: values derived from it are formed where used.
-// knn_wsel_kernel's compaction payloads 64 r + lane are loop invariants the
-// compiler otherwise hoists out of the query loop, one VGPR per register r
-// (109 -> 91 VGPRs; c2 +1.8%, profiles/r05_wsel_opaque_ab.log)
-__device__ inline int pcr_opaque(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
 // Waves per workgroup (one 64-query block), W, and the queries a wave takes
 // from the block's counter at a time, wsel_chunk<W>.  A launch of at most
 // 4096 waves at W = 8 (c2: 32 clouds x 16 blocks) leaves 4 waves per SIMD:
@@ -50,8 +50,9 @@ __device__ inline int pcr_opaque(int v) {
 // taking one query at a time, c2 +1.7% (profiles/r06_ab_wsel_waves.log,
 // r06_ab_wsel_chunk.log, r06_ab_wsel_pairs_waves.log; 10 waves -3%, 14 / 16
 // spill SGPRs, -12%).  Larger launches (pairs: 256 clouds) keep W = 8 with
-// two queries at a time: each wave stages the whole cloud in registers, and
-// 12 waves cost pairs 9% (312-315k against 341-343k clouds/s).
+// two queries at a time: each wave holds the whole cloud in registers, and
+// 12 waves cost pairs 9% (312-315k against 341-343k clouds/s, measured when
+// every wave still loaded the cloud from global memory).
 template <int W>
 constexpr int wsel_chunk() { return W == 8 ? 2 : 1; }
 // true: W = 8 (more than 4096 waves at W = 8), false: W = 12
@@ -185,24 +186,32 @@ __device__ inline unsigned long long wsel_sort64_exact(unsigned long long x, int
   return x;
 }
 
-// Appends the keys of the lanes in `m` (a ballot mask) to the wave's LDS
-// rows at slots base, base + 1, ...: d bits to kd, index to kd + 256 bytes.
-// exec = m for three VALU (the slot: mbcnt lo / hi; the address) and two
-// ds_write, restored after: no per-lane condition is materialised.
-__device__ inline void wsel_append(unsigned long long m, unsigned addr, unsigned d, int j) {
-  unsigned t;
+// Appends the keys of candidate register r's lanes in `m` (a ballot mask) to
+// the wave's LDS rows at slots base, base + 1, ...: d bits to kd, the sorted
+// position 64 r + lane to kd + 256 bytes, both by one ds_write2st64_b32.
+// The position is one VALU on the one lane register, 64 r an immediate (r is
+// a constant once the caller's loop is unrolled and this is inlined): as a
+// C++ expression the compiler hoists the R positions out of the query loop,
+// one VGPR each (109 instead of 91 VGPRs; c2 -1.8%,
+// profiles/r05_wsel_opaque_ab.log).  Then exec = m for three VALU (the slot:
+// mbcnt lo / hi; the address) and the write, restored after: no per-lane
+// condition is materialised.
+__device__ __attribute__((always_inline)) inline void wsel_append(unsigned long long m,
+                                                                  unsigned addr, unsigned d,
+                                                                  int lane, int r) {
+  unsigned t, p;
   unsigned long long save;
+  asm volatile("v_add_u32_e32 %0, %2, %1" : "=v"(p) : "v"(lane), "i"(64 * r));
   asm volatile(
       "s_mov_b64 %1, exec\n\t"
       "s_mov_b64 exec, %2\n\t"
       "v_mbcnt_lo_u32_b32 %0, %3, 0\n\t"
       "v_mbcnt_hi_u32_b32 %0, %4, %0\n\t"
       "v_lshl_add_u32 %0, %0, 2, %5\n\t"
-      "ds_write_b32 %0, %6\n\t"
-      "ds_write_b32 %0, %7 offset:256\n\t"
+      "ds_write2st64_b32 %0, %6, %7 offset1:1\n\t"
       "s_mov_b64 exec, %1"
       : "=&v"(t), "=&s"(save)
-      : "s"(m), "s"((unsigned)m), "s"((unsigned)(m >> 32)), "s"(addr), "v"(d), "v"(j)
+      : "s"(m), "s"((unsigned)m), "s"((unsigned)(m >> 32)), "s"(addr), "v"(d), "v"(p)
       : "memory");
 }
 
@@ -215,48 +224,54 @@ __global__ __launch_bounds__(W * 64) void knn_wsel_kernel(KnnSet s, int k) {
   __shared__ unsigned kbuf_s[kWselWaves][2][kWselCap];
   __shared__ int tile_s[kBlk][kSortedK + 1];  // output ids [query][slot] (padded: no bank conflicts)
   __shared__ int qnext_s;                     // the next chunk of the block's queries
-  __shared__ int cj_s[R * kBlk];              // original index of each sorted position
+  // the cloud's sorted coordinates and original indices (position p = 64 r +
+  // lane), staged once per workgroup: NaN / -1 from the cloud's end
+  __shared__ __align__(16) float cx_s[R * kBlk], cy_s[R * kBlk], cz_s[R * kBlk];
+  __shared__ __align__(16) int cj_s[R * kBlk];
   static_assert(sizeof(kbuf_s[0][0]) == 256, "wsel_append's offset");
+  static_assert(sizeof(cx_s) % (64 * 16) == 0, "whole LDS-DMA pieces");
   const int b = blockIdx.y, qblk = blockIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const size_t cb = (size_t)b * s.npad;
-  const int nr = s.npad / kBlk;  // candidate registers in use (<= R)
+  // One copy of the cloud per workgroup, by LDS-DMA (rows of npad elements at
+  // 256-byte aligned offsets; the last piece's lanes past the row re-read its
+  // last 16 bytes, and the arrays are whole pieces).  Rows shorter than the
+  // arrays: once the copy has landed, everything past the row becomes NaN / -1,
+  // so no position of the arrays is read unwritten.
+  lds_dma_copy<16>(cx_s, s.x + cb, 4 * s.npad);
+  lds_dma_copy<16>(cy_s, s.y + cb, 4 * s.npad);
+  lds_dma_copy<16>(cz_s, s.z + cb, 4 * s.npad);
+  lds_dma_copy<16>(cj_s, s.j + cb, 4 * s.npad);
+  if (threadIdx.x == 0) qnext_s = 0;
+  wait_vmcnt<0>();
+  __syncthreads();
+  if (s.npad < R * kBlk) {
+    for (int i = s.npad + threadIdx.x; i < R * kBlk; i += kWselWaves * kBlk) {
+      cx_s[i] = cy_s[i] = cz_s[i] = __builtin_nanf("");
+      cj_s[i] = -1;
+    }
+    __syncthreads();
+  }
   typedef float pf2v __attribute__((ext_vector_type(2)));
-  // the whole cloud, one candidate per lane and register (NaN padding); the
-  // candidates' original indices in LDS (cj_s[p], p = 64 r + lane: the
-  // compaction stores positions, the output looks the index up)
+  // the whole cloud, one candidate per lane and register: a register pair's
+  // positions are 64 dwords apart, one ds_read2st64_b32 (the compaction stores
+  // positions, the output looks the original index up in cj_s)
   pf2v cx[R / 2], cy[R / 2], cz[R / 2];
-  for (int i = threadIdx.x; i < R * kBlk; i += kWselWaves * kBlk)
-    cj_s[i] = i < s.npad ? s.j[cb + i] : -1;
 #pragma unroll
   for (int h = 0; h < R / 2; h++) {
-    float v[2][3];
-#pragma unroll
-    for (int e = 0; e < 2; e++) {
-      // unconditional loads (a register past the cloud re-reads its last
-      // block, then reads as NaN / -1): no branch, so all are in flight at once
-      const int r = 2 * h + e;
-      const bool ok = r < nr;
-      const size_t p = cb + (size_t)(ok ? r : nr - 1) * kBlk + lane;
-      const float x = s.x[p], y = s.y[p], z = s.z[p];
-      v[e][0] = ok ? x : __builtin_nanf("");
-      v[e][1] = ok ? y : __builtin_nanf("");
-      v[e][2] = ok ? z : __builtin_nanf("");
-    }
-    cx[h] = pf2v{v[0][0], v[1][0]};
-    cy[h] = pf2v{v[0][1], v[1][1]};
-    cz[h] = pf2v{v[0][2], v[1][2]};
+    const int p = 2 * h * kBlk + lane;
+    cx[h] = pf2v{cx_s[p], cx_s[p + kBlk]};
+    cy[h] = pf2v{cy_s[p], cy_s[p + kBlk]};
+    cz[h] = pf2v{cz_s[p], cz_s[p + kBlk]};
   }
   // the block's 64 queries, one per lane (every wave holds all of them: the
   // waves take chunks of kWselChunk consecutive queries from an LDS counter,
   // so a wave that drew expensive queries -- outliers, extra passes -- takes
   // fewer chunks and the workgroup ends with its mean, not its slowest wave)
-  const size_t pq = cb + (size_t)qblk * kBlk + lane;
-  const float qxl = s.x[pq], qyl = s.y[pq], qzl = s.z[pq];
-  const int qjl = s.j[pq];
-  if (threadIdx.x == 0) qnext_s = 0;
-  __syncthreads();
+  const int pq = qblk * kBlk + lane;
+  const float qxl = cx_s[pq], qyl = cy_s[pq], qzl = cz_s[pq];
+  const int qjl = cj_s[pq];
   auto grab = [&]() {
     int v = 0;
     if (lane == 0)
@@ -359,7 +374,7 @@ __global__ __launch_bounds__(W * 64) void knn_wsel_kernel(KnnSet s, int k) {
       for (int r = 0; r < R; r++) {
         const unsigned long long m = kKeep ? msk[kKeep ? r : 0] : __ballot(db[r] <= (unsigned)tb);
         if (m != 0ull) {
-          wsel_append(m, addr, db[r], 64 * r + pcr_opaque(lane));
+          wsel_append(m, addr, db[r], lane, r);
           addr += 4u * (unsigned)__popcll(m);
         }
       }
@@ -386,7 +401,7 @@ __global__ __launch_bounds__(W * 64) void knn_wsel_kernel(KnnSet s, int k) {
         const unsigned long long m =
             __ballot(db[r] < (unsigned)hi || (db[r] == (unsigned)hi && cj(r) <= jh));
         if (m != 0ull) {
-          wsel_append(m, addr, db[r], 64 * r + pcr_opaque(lane));
+          wsel_append(m, addr, db[r], lane, r);
           addr += 4u * (unsigned)__popcll(m);
         }
       }
