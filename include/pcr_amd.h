@@ -332,7 +332,23 @@ pcr_status pcr_extractor_voxel_stream_devox(int b, int c, int n, int r, int *cnt
  * corr12 [p, n1] = argmin_j, corr21 [p, n2] = argmin_i (first index on ties,
  * NaN first as np.argmin); idx1 / idx2 [p, n1] = the mutual pairs
  * (corr21[corr12[i]] == i) in ascending i, -1 after count[p] of them.
- * Channel sums are k-ordered fmaf chains (fp32 MFMA), include/pcr_math.h. */
+ * Channel sums are k-ordered fmaf chains (fp32 MFMA), include/pcr_math.h.
+ *
+ * Workspace keys (guaranteed): once the call's work on `stream` is done, the
+ * workspace holds the winning 64-bit key of every row and column, as
+ * include/pcr_math.h defines pcr_match_key: the mapped diff bits in the high
+ * word, the index in the low word.  rowbest [p][n1] at byte offset 0, colbest [p][n2] at byte
+ * offset p * n1 * 8 rounded up to a multiple of 256.  corr12 / corr21 are
+ * their low words.  Bytes of the workspace past colbest are never touched,
+ * and whatever the workspace held before the call does not matter.
+ *
+ * Alignment: f1 / f2 need only the alignment of a float.  With c % 4 == 0
+ * the row-major kernel reads the features as 16-byte vectors at addresses
+ * that are multiples of 4 bytes, not necessarily of 16: gfx950 global loads
+ * are dword-granular in the unaligned access mode ROCm configures, so a base
+ * pointer off a 16-byte boundary (a torch view starting at element 1) is
+ * legal and gives the same results, at more cache lines per load.  The
+ * workspace must be 8-byte aligned. */
 size_t pcr_mutual_nn_workspace_size(int p, int n1, int n2);
 pcr_status pcr_mutual_nn_match(const float *f1, const float *f2, int p, int n1, int n2, int c,
                                int *corr12, int *corr21, int *idx1, int *idx2, int *count,

@@ -26,6 +26,7 @@ _lib = None
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
+_u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
 _i = ctypes.c_int
 _f = ctypes.c_float
 
@@ -51,6 +52,8 @@ _SIGS = {
     "orc_sph_index_v": [_i, _f32p, _i, _i, _i32p],
     "orc_sph_index_ulp": [_i, _f32p, _i, _i, _i, _i32p],
     "orc_mutual_nn": [_i, _i, _i, _i, _f32p, _f32p, _i32p, _i32p, _i32p, _i32p, _i32p],
+    "orc_mutual_nn_keys": [_i, _i, _i, _i, _f32p, _f32p, _i32p, _i32p, _i32p, _i32p, _i32p, _u64p,
+                           _u64p],
     "orc_lrf": [_i, _i, _f32p, _f32p, _f32p, _i32p, _i32p],
     "orc_gather": [_i, _i, _i, _i, _f32p, _i32p, _f32p],
     "orc_gather_grad": [_i, _i, _i, _i, _f32p, _i32p, _f32p],
@@ -317,6 +320,26 @@ def mutual_nn(f1, f2):
     count = np.empty((p,), np.int32)
     lib().orc_mutual_nn(p, n1, n2, c, f1, f2, corr12, corr21, idx1, idx2, count)
     return corr12, corr21, idx1, idx2, count
+
+
+def mutual_nn_keys(f1, f2):
+    """mutual_nn plus the winning 64-bit pcr_match_key (include/pcr_math.h) of
+    every row and column: -> (corr12, corr21, idx1, idx2, count, rowbest
+    [p, n1], colbest [p, n2]), the keys as int64 (the bits the device keeps
+    in its workspace, as ops.mutual_nn_match(return_keys=True) views them)."""
+    f1, f2 = _f32(f1), _f32(f2)
+    p, n1, c = f1.shape
+    n2 = f2.shape[1]
+    corr12 = np.empty((p, n1), np.int32)
+    corr21 = np.empty((p, n2), np.int32)
+    idx1 = np.empty((p, n1), np.int32)
+    idx2 = np.empty((p, n1), np.int32)
+    count = np.empty((p,), np.int32)
+    rowbest = np.empty((p, n1), np.uint64)
+    colbest = np.empty((p, n2), np.uint64)
+    lib().orc_mutual_nn_keys(p, n1, n2, c, f1, f2, corr12, corr21, idx1, idx2, count, rowbest,
+                             colbest)
+    return corr12, corr21, idx1, idx2, count, rowbest.view(np.int64), colbest.view(np.int64)
 
 
 # ------------------------------------------------ LRF change_coords (f2)

@@ -550,8 +550,12 @@ void orc_sph_index_ulp(int n, const float *xyz, int r, int dacos, int datan, int
  * (datasets/deepgmr_mn40.py:232-244): f1 [p][n1][c], f2 [p][n2][c];
  * corr12 [p][n1] = argmin_j diff, corr21 [p][n2] = argmin_i diff; idx1 / idx2
  * [p][n1] the mutual pairs in ascending i (the rest -1), count [p]. */
-void orc_mutual_nn(int p, int n1, int n2, int c, const float *f1, const float *f2, int *corr12,
-                   int *corr21, int *idx1, int *idx2, int *count) {
+/* rowbest [p][n1] / colbest [p][n2] (either NULL: not returned): the winning
+ * pcr_match_key of every row / column, (diff bits mapped, index) -- what the
+ * device keeps in its workspace (include/pcr_amd.h) */
+void orc_mutual_nn_keys(int p, int n1, int n2, int c, const float *f1, const float *f2,
+                        int *corr12, int *corr21, int *idx1, int *idx2, int *count,
+                        unsigned long long *rowbest, unsigned long long *colbest_out) {
   int q;
 #pragma omp parallel for schedule(dynamic)
   for (q = 0; q < p; q++) {
@@ -579,8 +583,11 @@ void orc_mutual_nn(int p, int n1, int n2, int c, const float *f1, const float *f
         }
       }
       c12[i] = (int)(unsigned)(best & 0xFFFFFFFFull);
+      if (rowbest) rowbest[(size_t)q * n1 + i] = best;
     }
     for (j = 0; j < n2; j++) c21[j] = (int)(unsigned)(colbest[j] & 0xFFFFFFFFull);
+    if (colbest_out)
+      for (j = 0; j < n2; j++) colbest_out[(size_t)q * n2 + j] = colbest[j];
     for (i = 0; i < n1; i++) {
       if (c21[c12[i]] == i) {
         idx1[(size_t)q * n1 + cnt] = i;
@@ -594,6 +601,10 @@ void orc_mutual_nn(int p, int n1, int n2, int c, const float *f1, const float *f
     free(sq2);
     free(colbest);
   }
+}
+void orc_mutual_nn(int p, int n1, int n2, int c, const float *f1, const float *f2, int *corr12,
+                   int *corr21, int *idx1, int *idx2, int *count) {
+  orc_mutual_nn_keys(p, n1, n2, c, f1, f2, corr12, corr21, idx1, idx2, count, NULL, NULL);
 }
 
 /* ------------------------------------------------ LRF change_coords (f2) */

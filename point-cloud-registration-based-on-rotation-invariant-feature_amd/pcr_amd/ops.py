@@ -474,14 +474,17 @@ def estimate_normals(points, radius=0.1, return_counts=False):
     return (normals, counts) if return_counts else normals
 
 
-def mutual_nn_match(feat1, feat2, channel_major=False, workspace=None):
+def mutual_nn_match(feat1, feat2, channel_major=False, workspace=None, return_keys=False):
     """Feature-space mutual nearest neighbours of p registration pairs
     (datasets/deepgmr_mn40.py:232-244, batched): feat1 [p, n1, c],
     feat2 [p, n2, c] -> (corr12 [p, n1], corr21 [p, n2], idx1 [p, n1],
     idx2 [p, n1], count [p]); the first count[q] entries of idx1[q] / idx2[q]
     are the mutual pairs in ascending idx1, the rest -1.  channel_major:
     feat1 [p, c, n1], feat2 [p, c, n2] (the extractor's per-point layout),
-    matched in place."""
+    matched in place.  return_keys: also (rowbest [p, n1], colbest [p, n2]),
+    the winning 64-bit pcr_match_key of every row / column as int64 views of
+    the workspace (the layout include/pcr_amd.h guarantees; no copy, valid
+    until the workspace is reused)."""
     _check(feat1, "feat1")
     _check(feat2, "feat2")
     if feat1.dim() != 3 or feat2.dim() != 3 or feat1.shape[0] != feat2.shape[0]:
@@ -507,6 +510,11 @@ def mutual_nn_match(feat1, feat2, channel_major=False, workspace=None):
     _lib.check(fn(_ptr(feat1), _ptr(feat2), p, n1, n2, c, _ptr(corr12), _ptr(corr21),
                   _ptr(idx1), _ptr(idx2), _ptr(count), _ptr(ws), ws.numel(), _stream()),
                "mutual_nn_match")
+    if return_keys:
+        off = (p * n1 * 8 + 255) // 256 * 256
+        rowbest = ws[:p * n1 * 8].view(torch.int64).view(p, n1)
+        colbest = ws[off:off + p * n2 * 8].view(torch.int64).view(p, n2)
+        return corr12, corr21, idx1, idx2, count, rowbest, colbest
     return corr12, corr21, idx1, idx2, count
 
 
