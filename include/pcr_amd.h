@@ -512,6 +512,41 @@ pcr_status pcr_teaser(const float *xyz1, const float *xyz2, int p, int n1, int n
                       int *inliers, int *num_inliers, int *iterations, int *status,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------- grid subsampling --------------------------
+ * cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.cpp
+ * (utils/grid_subsampleing.py grid_sub_sampling: KPConv's voxel-grid
+ * barycentres), for b ragged clouds (the scalar math and the
+ * deviations from the reference are include/pcr_gridsub.h).
+ *   xyz [b,3,n], features [b,c,n] (NULL with c = 0); counts_in [b]: cloud q's
+ *   valid points are its first counts_in[q] (NULL: all n).  cell: the cell size.
+ *   Per cloud, in fp32: origin_d = floorf(min_d * (1.0f / cell)) * cell over
+ *   the valid points, N_d = max(0, floorf((max_d - origin_d) / cell)) + 1, a
+ *   point's index i_d = max(0, floorf((p_d - origin_d) / cell)) and its key
+ *   ix + NX * (iy + NY * iz) (64 bit).  Every distinct key is a cell; its sums
+ *   start at 0.0f and take the cell's points in ascending point index.
+ *   out_xyz = sum * (float)(1.0 / (double)count), out_features = sum /
+ *   (float)count.  Cells are output in ascending key.
+ *   out_xyz [b,3,n], out_features [b,c,n] (NULL with c = 0): slot s < out_count
+ *   is cell s, later slots hold 0; out_count [b]; cell_of [b,n]: the output
+ *   slot of each input point, -1 past the valid count; cell_count [b,n]: points
+ *   per slot, 0 past out_count; origin [b,3]; dims [b,3] = N_d (saturated at
+ *   2^30 + 1); status [b]: 0 ok, 1 valid count outside [1, n], 2 a non-finite
+ *   coordinate among the valid points, 3 some N_d > 2^20 or an origin that is
+ *   not finite.  With a status other than 0: out_count 0, every slot 0,
+ *   cell_of -1 (origin and dims 0 with status 1 / 2).  Every output element is
+ *   written.  b, n, c >= 0 (n >= 1 when b > 0), b * n < 2^31; cell finite and
+ *   > 0.  A bad cloud never fails the call and touches no other cloud.
+ * Bit-identical from run to run (no float atomics: a stable sort orders every
+ * cell's sum).  Runs on `stream`, no host sync; the workspace
+ * (pcr_grid_subsample_workspace_size bytes: 40 + 4 c bytes per point, 1 KB per
+ * 1024 points and 2 KB per cloud) is the caller's. */
+size_t pcr_grid_subsample_workspace_size(int b, int n, int c);
+pcr_status pcr_grid_subsample(const float *xyz, const float *features, const int *counts_in,
+                              int b, int n, int c, float cell, float *out_xyz,
+                              float *out_features, int *out_count, int *cell_of, int *cell_count,
+                              float *origin, int *dims, int *status, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
 /* ------------------------------------ LRF change_coords (8f f2) ----------
  * models/pvcnn_classify.py:153-184 (rot_invariant_preprocess ==
  * 'change_coords'), one cloud per workgroup, no host round trip.

@@ -11,6 +11,9 @@ format, the ModelNet40 sample pipeline around it, and GPU normals.
   same rotation.
 - ``get_normals`` is utils/open3d_func.py:77-83 on the GPU
   (``ops.estimate_normals``, radius 0.1).
+- ``grid_sub_sampling`` is utils/grid_subsampleing.py's wrapper of KPConv's
+  grid subsampling on the GPU (``ops.grid_subsample``), for one numpy cloud;
+  ``pad_clouds`` builds the ragged batch the op takes.
 
 The DeepGMR h5 test files (datasets/deepgmr_mn40.py:46-49) need h5py, which
 is not installed; they are out of reach here.
@@ -121,3 +124,65 @@ def get_normals(points, radius=0.1):
     if points.dim() == 2:
         return ops.estimate_normals(points.t().contiguous()[None], radius)[0].t()
     return ops.estimate_normals(points.contiguous(), radius)
+
+
+def pad_clouds(clouds):
+    """A ragged batch for ``ops.grid_subsample``: clouds, a list of [3, n_i]
+    arrays or tensors -> (xyz [b, 3, n_max] float32, zero padded; counts [b]
+    int32).  Tensors in, tensors out (on the first cloud's device); numpy in,
+    numpy out."""
+    if len(clouds) == 0:
+        raise ValueError("pad_clouds: no clouds")
+    for x in clouds:
+        if len(x.shape) != 2 or x.shape[0] != 3:
+            raise ValueError("pad_clouds: expected [3, n] clouds, got %s" % (tuple(x.shape),))
+    sizes = [int(x.shape[1]) for x in clouds]
+    b, n = len(clouds), max(max(sizes), 1)
+    if isinstance(clouds[0], np.ndarray):
+        xyz = np.zeros((b, 3, n), np.float32)
+        for q, x in enumerate(clouds):
+            xyz[q, :, :sizes[q]] = x
+        return xyz, np.asarray(sizes, np.int32)
+    import torch
+    dev = clouds[0].device
+    xyz = torch.zeros((b, 3, n), dtype=torch.float32, device=dev)
+    for q, x in enumerate(clouds):
+        xyz[q, :, :sizes[q]] = x
+    return xyz, torch.tensor(sizes, dtype=torch.int32, device=dev)
+
+
+def grid_sub_sampling(points, features=None, labels=None, grid_size=0.1, verbose=0):
+    """utils/grid_subsampleing.py grid_sub_sampling on the GPU
+    (``ops.grid_subsample``): one cloud, points (N, 3) and features (N, d)
+    numpy -> subsampled points (M, 3) float32, and features (M, d) when given.
+    The cells come in ascending cell key (the reference's order is that of a
+    hash map).  labels raise: the reference's majority vote breaks ties by
+    hash-map order, which cannot be pinned; vote with ``cell_of`` of
+    ``ops.grid_subsample`` instead."""
+    import torch
+    from . import ops
+    del verbose
+    if labels is not None:
+        raise RuntimeError("grid_sub_sampling: labels are not supported (the reference's vote "
+                           "breaks ties by hash-map order); vote with ops.grid_subsample's "
+                           "cell_of")
+    points = np.asarray(points)
+    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise RuntimeError("grid_sub_sampling: expected points (N, 3) with N >= 1")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    xyz = torch.from_numpy(np.ascontiguousarray(points.T, np.float32))[None].to(dev)
+    feat = None
+    if features is not None:
+        features = np.asarray(features)
+        if features.ndim != 2 or features.shape[0] != points.shape[0]:
+            raise RuntimeError("grid_sub_sampling: expected features (N, d)")
+        feat = torch.from_numpy(np.ascontiguousarray(features.T, np.float32))[None].to(dev)
+    out = ops.grid_subsample(xyz, grid_size, feat)
+    if int(out["status"][0]) != 0:
+        raise RuntimeError("grid_sub_sampling: status %d (2: a non-finite coordinate, 3: the "
+                           "grid is finer than 2^20 cells along an axis)" % int(out["status"][0]))
+    m = int(out["count"][0])
+    sub = out["xyz"][0, :, :m].t().contiguous().cpu().numpy()
+    if feat is None:
+        return sub
+    return sub, out["features"][0, :, :m].t().contiguous().cpu().numpy()

@@ -698,3 +698,49 @@ def teaser(xyz1, xyz2, idx1, idx2, count, noise_bound=0.02, cbar2=1.0, gnc_facto
         _ptr(inliers), _ptr(num_inliers), _ptr(iterations), _ptr(status), _ptr(ws), ws.numel(),
         _stream()), "teaser")
     return transform, clique, clique_size, inliers, num_inliers, iterations, status
+
+
+def grid_subsample(xyz, cell, features=None, counts=None):
+    """Grid subsampling (voxel-grid barycentres) of b ragged clouds
+    (cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.cpp,
+    utils/grid_subsampleing.py grid_sub_sampling, batched):
+    xyz [b, 3, n], cell the cell size, features [b, c, n] or None, counts [b]
+    int32 -- cloud q's valid points are its first counts[q] -- or None for all
+    n -> a dict: xyz [b, 3, n] and features [b, c, n] (None without features)
+    hold the cells' barycentres in slots 0 .. count - 1, in ascending cell key,
+    and 0 after them; count [b]; cell_of [b, n] the output slot of every input
+    point (-1 past the valid count); cell_count [b, n] the points per slot;
+    origin [b, 3] and dims [b, 3] of the grid; status [b]: 0 ok, 1 valid count
+    outside [1, n], 2 a non-finite coordinate, 3 a grid finer than 2^20 cells
+    along an axis (count 0 for those clouds).  Every cell sums its points in
+    ascending point index: bit-identical from run to run."""
+    _check(xyz, "xyz")
+    if xyz.dim() != 3 or xyz.shape[1] != 3 or xyz.shape[2] < 1:
+        raise RuntimeError("grid_subsample: expected xyz [b, 3, n] with n >= 1")
+    b, _, n = xyz.shape
+    c = 0
+    if features is not None:
+        _check(features, "features")
+        if features.dim() != 3 or features.shape[0] != b or features.shape[2] != n:
+            raise RuntimeError("grid_subsample: expected features [b, c, n]")
+        c = features.shape[1]
+    if counts is not None:
+        _check(counts, "counts", "int")
+        if tuple(counts.shape) != (b,):
+            raise RuntimeError("grid_subsample: expected counts [b]")
+    dev = xyz.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out_xyz = torch.empty((b, 3, n), **f32)
+    out_feat = torch.empty((b, c, n), **f32) if features is not None else None
+    count, status = torch.empty((b,), **i32), torch.empty((b,), **i32)
+    cell_of, cell_count = torch.empty((b, n), **i32), torch.empty((b, n), **i32)
+    origin, dims = torch.empty((b, 3), **f32), torch.empty((b, 3), **i32)
+    lib = _lib.load()
+    ws = _workspace(lib.pcr_grid_subsample_workspace_size(b, n, c), dev)
+    _lib.check(lib.pcr_grid_subsample(
+        _ptr(xyz), _ptr(features) if c else None, _ptr(counts), b, n, c, float(cell), _ptr(out_xyz),
+        _ptr(out_feat) if c else None, _ptr(count), _ptr(cell_of), _ptr(cell_count), _ptr(origin),
+        _ptr(dims), _ptr(status), _ptr(ws), ws.numel(), _stream()), "grid_subsample")
+    return dict(xyz=out_xyz, features=out_feat, count=count, cell_of=cell_of,
+                cell_count=cell_count, origin=origin, dims=dims, status=status)
