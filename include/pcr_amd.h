@@ -547,6 +547,38 @@ pcr_status pcr_grid_subsample(const float *xyz, const float *features, const int
                               float *origin, int *dims, int *status, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* ------------------------------- FPFH descriptors --------------------------
+ * Open3D's compute_fpfh_feature (ComputeFPFHFeature with
+ * KDTreeSearchParamHybrid(radius, max_nn)), the training-free descriptor its
+ * registration functions (utils/open3d_func.py:43-59) are normally paired
+ * with, for b clouds (the scalar math is include/pcr_fpfh.h,
+ * an fp32 restatement whose operation order is the contract).
+ *   xyz [b,3,n], normals [b,3,n]; nbr_idx [b,k,n] and nbr_dist [b,k,n] exactly
+ *   as pcr_knn_forward writes them for a cloud against itself (squared L2,
+ *   ascending).  The op does not search.  Of the slots s < min(k, n), in
+ *   ascending s, slot (j, d) is in N(i) when 0 <= j < n, j != i and 0 < d <=
+ *   radius * radius (fp32; a NaN d fails); any other j is never an address.
+ *   Every pair (i, j in N(i)) counts in three of 33 bins (pcr_fpfh_pair,
+ *   pcr_fpfh_bins); spfh[i][c] = (float)count_c * (100.0f / (float)m) with m =
+ *   |N(i)|, 0 when m = 0; acc_c = the sum over N(i) in ascending slot of
+ *   spfh[j][c] / d from 0.0f; per group of 11 channels S = the sum of its acc
+ *   in ascending channel from 0.0f; fpfh[i][c] = acc_c * (100.0f / S) +
+ *   spfh[i][c] (acc_c + spfh[i][c] when S = 0).
+ *   fpfh [b,33,n] (the layout pcr_mutual_nn_match_cm takes); spfh [b,33,n] and
+ *   nbr_count [b,n] = m may be NULL.  Every output element is written.
+ *   n >= 1, 1 <= k <= 128, radius finite and > 0, b * k * n < 2^31; b = 0
+ *   returns PCR_OK.  A bad point (NaN coordinate or normal) never fails the
+ *   call and touches only itself and the points that list it; no cloud touches
+ *   another.
+ * Bit-identical from run to run (integer bin counts, serial sums, no float
+ * atomics).  Runs on `stream`; the workspace (pcr_fpfh_workspace_size bytes:
+ * 164 bytes per point, each part rounded up to 256) is the caller's. */
+size_t pcr_fpfh_workspace_size(int b, int n);
+pcr_status pcr_fpfh(const float *xyz, const float *normals, const int *nbr_idx,
+                    const float *nbr_dist, int b, int n, int k, float radius, float *fpfh,
+                    float *spfh, int *nbr_count, void *workspace, size_t workspace_bytes,
+                    void *stream);
+
 /* ------------------------------------ LRF change_coords (8f f2) ----------
  * models/pvcnn_classify.py:153-184 (rot_invariant_preprocess ==
  * 'change_coords'), one cloud per workgroup, no host round trip.

@@ -744,3 +744,55 @@ def grid_subsample(xyz, cell, features=None, counts=None):
         _ptr(dims), _ptr(status), _ptr(ws), ws.numel(), _stream()), "grid_subsample")
     return dict(xyz=out_xyz, features=out_feat, count=count, cell_of=cell_of,
                 cell_count=cell_count, origin=origin, dims=dims, status=status)
+
+
+# ------------------------------------------------ FPFH descriptors (4.8f)
+def fpfh_from_neighbors(xyz, normals, nbr_idx, nbr_dist, radius, return_spfh=False,
+                        return_counts=False):
+    """FPFH descriptors (Open3D's compute_fpfh_feature, batched; DESIGN.md
+    4.8f, include/pcr_fpfh.h) from ready neighbour lists: xyz [b, 3, n],
+    normals [b, 3, n], nbr_idx [b, k, n] int32 and nbr_dist [b, k, n] as
+    knn_forward_cuda(xyz, xyz, k) returns them (squared distances, ascending;
+    k <= 128) -> fpfh [b, 33, n], the channel-major layout of
+    mutual_nn_match(channel_major=True).  A point's neighbours are the listed
+    points other than itself within `radius`.  return_spfh: also the stage-1
+    histograms [b, 33, n]; return_counts: also the neighbour counts [b, n]
+    int32 (in that order).  Bit-identical from run to run."""
+    _check(xyz, "xyz")
+    _check(normals, "normals")
+    _check(nbr_idx, "nbr_idx", "int")
+    _check(nbr_dist, "nbr_dist")
+    if xyz.dim() != 3 or xyz.shape[1] != 3 or xyz.shape[2] < 1:
+        raise RuntimeError("fpfh: expected xyz [b, 3, n] with n >= 1")
+    b, _, n = xyz.shape
+    if tuple(normals.shape) != (b, 3, n):
+        raise RuntimeError("fpfh: expected normals [b, 3, n]")
+    if nbr_idx.dim() != 3 or nbr_idx.shape[0] != b or nbr_idx.shape[2] != n or \
+            nbr_idx.shape != nbr_dist.shape:
+        raise RuntimeError("fpfh: expected nbr_idx and nbr_dist [b, k, n]")
+    k = nbr_idx.shape[1]
+    dev = xyz.device
+    out = torch.empty((b, 33, n), dtype=torch.float32, device=dev)
+    spfh = torch.empty((b, 33, n), dtype=torch.float32, device=dev) if return_spfh else None
+    counts = torch.empty((b, n), dtype=torch.int32, device=dev) if return_counts else None
+    lib = _lib.load()
+    ws = _workspace(lib.pcr_fpfh_workspace_size(b, n), dev)
+    _lib.check(lib.pcr_fpfh(
+        _ptr(xyz), _ptr(normals), _ptr(nbr_idx), _ptr(nbr_dist), b, n, k, float(radius), _ptr(out),
+        _ptr(spfh), _ptr(counts), _ptr(ws), ws.numel(), _stream()), "fpfh")
+    res = (out,) + ((spfh,) if return_spfh else ()) + ((counts,) if return_counts else ())
+    return res if len(res) > 1 else out
+
+
+def fpfh(xyz, normals, radius, k=100, return_spfh=False, return_counts=False):
+    """FPFH descriptors of b clouds from points and normals alone: the
+    neighbour lists of knn_forward_cuda(xyz, xyz, min(k, 128)), then
+    fpfh_from_neighbors.  k counts the point itself, as the max_nn of Open3D's
+    KDTreeSearchParamHybrid(radius, max_nn) does."""
+    _check(xyz, "xyz")
+    _check(normals, "normals")
+    k = min(int(k), 128)
+    if k < 1:
+        raise RuntimeError("fpfh: k must be at least 1")
+    dist, _, idx, _ = knn_forward_cuda(xyz, xyz, k)
+    return fpfh_from_neighbors(xyz, normals, idx, dist, radius, return_spfh, return_counts)

@@ -27,7 +27,9 @@ reference's func='fgr' solver) is the other estimate from the
 correspondences: fgr_pairs, or solver="fgr" of register / register_pairs.
 ops.teaser (the reference's func='teaserpp' solver with a bounded clique
 search) is the one meant for mostly wrong matches:
-teaser_pairs, or solver="teaser".
+teaser_pairs, or solver="teaser".  fpfh_pairs needs no extractor and no
+weights: it computes FPFH descriptors (ops.fpfh) from the
+points and normals of both clouds and hands them to register_pairs.
 
 The native runner (pcr_extractor_run with match_pairs = P) enqueues the
 matching on each step's voxel queue right after its devox (behind the grid
@@ -264,3 +266,19 @@ def alignment_rmse(xyz1, gt, est):
     gt, est = gt.to(torch.float64), est.to(torch.float64)
     return torch.linalg.norm(apply_transform(xyz1, est) - apply_transform(xyz1, gt), dim=1).mean(
         dim=1)
+
+
+def fpfh_pairs(xyz1, normals1, xyz2, normals2, radius, k=100, solver="ransac", icp=None,
+               **solver_args):
+    """Two clouds with normals in, transform out, with nothing trained: the
+    FPFH descriptors of both clouds (ops.fpfh with `radius` and `k`; DESIGN.md
+    4.8f), then register_pairs on them (channel-major, 33 channels) with
+    `solver`, `icp` and the solver's keyword arguments.  xyz [p, 3, n] and
+    normals [p, 3, n] per side -> register_pairs' dict plus feat1 [p, 33, n1]
+    and feat2 [p, 33, n2]."""
+    feat1 = ops.fpfh(xyz1, normals1, radius, k)
+    feat2 = ops.fpfh(xyz2, normals2, radius, k)
+    out = register_pairs(xyz1, xyz2, feat1, feat2, channel_major=True, icp=icp, solver=solver,
+                         **solver_args)
+    out["feat1"], out["feat2"] = feat1, feat2
+    return out
