@@ -579,6 +579,37 @@ pcr_status pcr_fpfh(const float *xyz, const float *normals, const int *nbr_idx,
                     float *spfh, int *nbr_count, void *workspace, size_t workspace_bytes,
                     void *stream);
 
+/* ------------------------- hybrid (radius + max_nn) neighbour search -------
+ * Open3D's KDTreeSearchParamHybrid(radius, max_nn) of b ragged clouds against
+ * themselves: the search pcr_fpfh's neighbour sets are defined on (DESIGN.md
+ * 4.8g; the scalar math is include/pcr_hybrid.h).
+ *   xyz [b,3,n]; counts [b]: cloud q's valid points are its first counts[q]
+ *   (clamped to [0, n]; NULL: all n).  d(i, j) = fmaf(tz, tz, fmaf(ty, ty, tx *
+ *   tx)) with t = p_i - p_j in fp32, pcr_knn_forward's distance bit for bit; j
+ *   is within the radius of i when d <= radius * radius (fp32; a NaN or
+ *   infinite d fails).  The row of a valid query i lists the valid j within
+ *   its radius (i itself included), ascending by (bits of d, j) -- ties go to
+ *   the lower index -- cut to the first k (max_nn).
+ *   nbr_dist [b,k,n] and nbr_idx [b,k,n], slot-major as pcr_fpfh reads them;
+ *   unfilled slots hold (+inf, -1).  nbr_count [b,n]: the filled slots.
+ *   within [b,n] (may be NULL): the points within the radius before the cut.
+ *   A query at or past counts[q] has no filled slot and both counts 0, and so
+ *   has a point with a non-finite coordinate, which is in no row either.
+ *   Every output element is written.  n >= 1, 1 <= k <= 128, radius and
+ *   radius * radius finite and > 0, b * k * n < 2^31; b = 0 returns PCR_OK.
+ * The result is that rule for every input: the cell grid the kernels use
+ * (side >= radius * (1 + 2^-8), at most 32 cells an axis, one cell where its
+ * parameters cannot be formed) never changes it.  Bit-identical from run to
+ * run (selection on the 64-bit key; integer atomics only).  Runs on `stream`,
+ * no host sync; the workspace (pcr_hybrid_search_workspace_size bytes, a
+ * function of b and n alone: 20 bytes per point, 8 per cell of a grid of g^3
+ * cells, g the smallest with 2 g^3 >= n and at most 32, 2.1 KB per cloud) is
+ * the caller's. */
+size_t pcr_hybrid_search_workspace_size(int b, int n);
+pcr_status pcr_hybrid_search(const float *xyz, const int *counts, int b, int n, int k,
+                             float radius, float *nbr_dist, int *nbr_idx, int *nbr_count,
+                             int *within, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------ LRF change_coords (8f f2) ----------
  * models/pvcnn_classify.py:153-184 (rot_invariant_preprocess ==
  * 'change_coords'), one cloud per workgroup, no host round trip.

@@ -88,6 +88,8 @@ SIGNATURES = {
     "pcr_grid_subsample": (ST, [P, P, P, I, I, I, F, P, P, P, P, P, P, P, P, P, SZ, P]),
     "pcr_fpfh_workspace_size": (SZ, [I, I]),
     "pcr_fpfh": (ST, [P, P, P, P, I, I, I, F, P, P, P, P, SZ, P]),
+    "pcr_hybrid_search_workspace_size": (SZ, [I, I]),
+    "pcr_hybrid_search": (ST, [P, P, I, I, I, F, P, P, P, P, P, SZ, P]),
     "pcr_lrf_change_coords": (ST, [P, I, I, P, P, P, P, P]),
     "pcr_gather_features_forward": (ST, [P, P, I, I, I, I, P, P]),
     "pcr_gather_features_backward": (ST, [P, P, I, I, I, I, P, P]),

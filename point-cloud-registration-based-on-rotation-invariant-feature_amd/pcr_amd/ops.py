@@ -784,15 +784,63 @@ def fpfh_from_neighbors(xyz, normals, nbr_idx, nbr_dist, radius, return_spfh=Fal
     return res if len(res) > 1 else out
 
 
-def fpfh(xyz, normals, radius, k=100, return_spfh=False, return_counts=False):
-    """FPFH descriptors of b clouds from points and normals alone: the
-    neighbour lists of knn_forward_cuda(xyz, xyz, min(k, 128)), then
-    fpfh_from_neighbors.  k counts the point itself, as the max_nn of Open3D's
-    KDTreeSearchParamHybrid(radius, max_nn) does."""
+def fpfh(xyz, normals, radius, k=100, return_spfh=False, return_counts=False, search="knn",
+         counts=None):
+    """FPFH descriptors of b clouds from points and normals alone: neighbour
+    lists, then fpfh_from_neighbors.  k counts the point itself, as the max_nn
+    of Open3D's KDTreeSearchParamHybrid(radius, max_nn) does.  search="knn":
+    the lists of knn_forward_cuda(xyz, xyz, min(k, 128)); search="grid": those
+    of hybrid_search(xyz, radius, min(k, 128), counts), which
+    also takes ragged clouds: counts [b] int32, cloud q's valid points are its
+    first counts[q]; the points past them get zero descriptors."""
     _check(xyz, "xyz")
     _check(normals, "normals")
     k = min(int(k), 128)
     if k < 1:
         raise RuntimeError("fpfh: k must be at least 1")
-    dist, _, idx, _ = knn_forward_cuda(xyz, xyz, k)
+    if search not in ("knn", "grid"):
+        raise RuntimeError("fpfh: search must be 'knn' or 'grid' (got %r)" % (search,))
+    if search == "knn":
+        if counts is not None:
+            raise RuntimeError("fpfh: counts needs search='grid'")
+        dist, _, idx, _ = knn_forward_cuda(xyz, xyz, k)
+    else:
+        dist, idx, _ = hybrid_search(xyz, radius, k, counts)
     return fpfh_from_neighbors(xyz, normals, idx, dist, radius, return_spfh, return_counts)
+
+
+# ------------------------------------- hybrid neighbour search (4.8g)
+def hybrid_search(xyz, radius, k, counts=None, return_within=False):
+    """Hybrid (radius + max_nn) neighbour search of b clouds against
+    themselves (Open3D's KDTreeSearchParamHybrid(radius, max_nn), batched;
+    DESIGN.md 4.8g, include/pcr_hybrid.h): xyz [b, 3, n], k <= 128 counting
+    the point itself, counts [b] int32 -- cloud q's valid points are its first
+    counts[q] -- or None for all n -> dist [b, k, n] (squared, knn_forward_cuda's
+    distance bit for bit), idx [b, k, n] int32, count [b, n] int32: per query
+    the valid points within `radius`, ascending by (distance, index), cut to
+    k; unfilled slots hold (+inf, -1).  return_within: also within [b, n]
+    int32, the points within the radius before the cut.  A query past its
+    cloud's count, or with a non-finite coordinate, has an empty row.
+    Bit-identical from run to run."""
+    _check(xyz, "xyz")
+    if xyz.dim() != 3 or xyz.shape[1] != 3 or xyz.shape[2] < 1:
+        raise RuntimeError("hybrid_search: expected xyz [b, 3, n] with n >= 1")
+    b, _, n = xyz.shape
+    k = int(k)
+    if k < 1 or k > 128:
+        raise RuntimeError("hybrid_search: k must be in [1, 128] (got %d)" % k)
+    if counts is not None:
+        _check(counts, "counts", "int")
+        if tuple(counts.shape) != (b,):
+            raise RuntimeError("hybrid_search: expected counts [b]")
+    dev = xyz.device
+    dist = torch.empty((b, k, n), dtype=torch.float32, device=dev)
+    idx = torch.empty((b, k, n), dtype=torch.int32, device=dev)
+    count = torch.empty((b, n), dtype=torch.int32, device=dev)
+    within = torch.empty((b, n), dtype=torch.int32, device=dev) if return_within else None
+    lib = _lib.load()
+    ws = _workspace(lib.pcr_hybrid_search_workspace_size(b, n), dev)
+    _lib.check(lib.pcr_hybrid_search(
+        _ptr(xyz), _ptr(counts), b, n, k, float(radius), _ptr(dist), _ptr(idx), _ptr(count),
+        _ptr(within), _ptr(ws), ws.numel(), _stream()), "hybrid_search")
+    return (dist, idx, count, within) if return_within else (dist, idx, count)

@@ -269,15 +269,16 @@ def alignment_rmse(xyz1, gt, est):
 
 
 def fpfh_pairs(xyz1, normals1, xyz2, normals2, radius, k=100, solver="ransac", icp=None,
-               **solver_args):
+               search="knn", **solver_args):
     """Two clouds with normals in, transform out, with nothing trained: the
-    FPFH descriptors of both clouds (ops.fpfh with `radius` and `k`; DESIGN.md
-    4.8f), then register_pairs on them (channel-major, 33 channels) with
+    FPFH descriptors of both clouds (ops.fpfh with `radius`, `k` and `search`:
+    "knn" or "grid", the neighbour search behind the descriptor; DESIGN.md
+    4.8f, 4.8g), then register_pairs on them (channel-major, 33 channels) with
     `solver`, `icp` and the solver's keyword arguments.  xyz [p, 3, n] and
     normals [p, 3, n] per side -> register_pairs' dict plus feat1 [p, 33, n1]
     and feat2 [p, 33, n2]."""
-    feat1 = ops.fpfh(xyz1, normals1, radius, k)
-    feat2 = ops.fpfh(xyz2, normals2, radius, k)
+    feat1 = ops.fpfh(xyz1, normals1, radius, k, search=search)
+    feat2 = ops.fpfh(xyz2, normals2, radius, k, search=search)
     out = register_pairs(xyz1, xyz2, feat1, feat2, channel_major=True, icp=icp, solver=solver,
                          **solver_args)
     out["feat1"], out["feat2"] = feat1, feat2
