@@ -617,7 +617,9 @@ pcr_status pcr_hybrid_search(const float *xyz, const int *counts, int b, int n, 
  * oracle/pcr_oracle.c orc_lrf); base_x = the point of largest norm; base_y =
  * the next point in descending-norm rank with norm >= 1e-5 and
  * |<base_x, p/|p|>| < 0.9; Gram-Schmidt, base_z = x cross y; new_coords =
- * basis . nc.  Rank ties go to the lower index.
+ * basis . nc.  Rank ties go to the lower index; a NaN norm ranks first (as in
+ * torch.argsort, descending), so a cloud with a NaN or infinite coordinate
+ * has status 1.
  *   coords [b,3,n] -> new_coords [b,3,n], basis [b,3,3] (rows x, y, z),
  *   picks [b,2] (base_x, base_y point indices), status [b]: 0 ok, 1 base_x
  *   norm <= 1e-5, 2 no base_y, 3 degenerate Gram-Schmidt.  These are the

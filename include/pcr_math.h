@@ -543,9 +543,12 @@ PCR_HD float pcr_dot3f_nofma(float a0, float a1, float a2, float b0, float b1, f
   float s = p0 + p1;
   return s + p2;
 }
-/* larger key = earlier in the descending-norm rank; NaN norms never win */
+/* larger key = earlier in the descending-norm rank.  A NaN norm ranks before
+ * every number, as in torch.argsort(descending=True): it becomes base_x and
+ * fails the first assert (:159), also where other norms are infinite. */
 PCR_HD unsigned long long pcr_rank_key(float nrm, int idx) {
   unsigned u;
+  if (nrm != nrm) return (0xFFFFFFFFull << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)idx);
   if (!(nrm >= 0.0f)) return 0ull;
   __builtin_memcpy(&u, &nrm, 4);
   return ((unsigned long long)(u + 1u) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)idx);

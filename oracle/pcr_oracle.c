@@ -620,7 +620,7 @@ static int lrf_rank_cmp(const void *pa, const void *pb) {
   int a = *(const int *)pa, b = *(const int *)pb;
   float na = lrf_sort_norms[a], nb = lrf_sort_norms[b];
   int a_nan = !(na == na), b_nan = !(nb == nb);
-  if (a_nan != b_nan) return a_nan - b_nan; /* NaN last */
+  if (a_nan != b_nan) return b_nan - a_nan; /* NaN first, as torch.argsort(descending) */
   if (!a_nan && na != nb) return na > nb ? -1 : 1;
   return a - b;
 }
@@ -649,19 +649,13 @@ void orc_lrf(int b, int n, const float *coords, float *new_coords, float *basis,
     }
     for (a = 0; a < 9; a++) B[a] = 0.0f;
     i0 = rank[0];
-    if (!(nr[i0] == nr[i0])) i0 = -1; /* every norm NaN */
-    if (i0 < 0) {
-      st = 1;
-    } else {
-      for (a = 0; a < 3; a++) p0[a] = nc[i0 + a * n];
-      n0 = nr[i0];
-      if (!(n0 > 1e-5f)) st = 1;
-      for (a = 0; a < 3; a++) bx[a] = p0[a] / n0;
-    }
+    for (a = 0; a < 3; a++) p0[a] = nc[i0 + a * n];
+    n0 = nr[i0];
+    if (!(n0 > 1e-5f)) st = 1; /* a NaN norm ranks first and fails here */
+    for (a = 0; a < 3; a++) bx[a] = p0[a] / n0;
     if (st == 0) {
       for (j = 1; j < n; j++) {
         int q = rank[j];
-        if (!(nr[q] == nr[q])) break; /* NaN ranks after every number */
         if (pcr_lrf_base_y_ok(nc[q], nc[q + n], nc[q + 2 * n], nr[q], bx)) {
           i1 = q;
           break;

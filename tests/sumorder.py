@@ -105,3 +105,41 @@ def grouping_backward_bound(grad_y, idx, n):
         np.add.at(S[bi], (slice(None), ids), np.abs(grad_y[bi].reshape(c, -1)).astype(np.float64))
         np.add.at(M[bi][0], ids, 1)
     return _bound(S, M)
+
+
+def _scatter_sums(ids, terms, size):
+    """ids [b, k] targets, terms [b, c, k] >= 0 -> (sum of the valid terms per
+    target [b, c, size], number of them [b, 1, size]); ids outside [0, size)
+    drop.  One np.bincount per channel over all clouds at once, so many small
+    clouds cost no more than one large one."""
+    ids = np.asarray(ids, np.int64)
+    b, c, _ = terms.shape
+    ok = (ids >= 0) & (ids < size)
+    flat = (np.arange(b, dtype=np.int64)[:, None] * size + ids)[ok]
+    M = np.bincount(flat, minlength=b * size).reshape(b, 1, size)
+    S = np.empty((b, c, size), np.float64)
+    for ch in range(c):
+        S[:, ch] = np.bincount(flat, weights=terms[:, ch][ok], minlength=b * size).reshape(b, size)
+    return S, M
+
+
+def gather_backward_bound(grad_y, idx, n):
+    """Per-element bound [b, c, n] for gather_features_backward
+    (sampling.cu:53-67): grad_x[c, idx[j]] += grad_y[c, j] for the idx inside
+    [0, n)."""
+    S, M = _scatter_sums(idx, np.abs(np.asarray(grad_y, np.float32)), n)
+    return _bound(S, M)
+
+
+def three_nn_backward_bound(grad_y, inds, wgts, m):
+    """Per-element bound [b, c, m] for three_nearest_neighbors_interpolate_
+    backward (neighbor_interpolate.cu:146-171): grad_x[c, inds[a, j]] +=
+    fl(wgts[a, j] * grad_y[c, j]) over the three slots a, for the inds inside
+    [0, m)."""
+    grad_y = np.asarray(grad_y, np.float32)
+    wgts = np.asarray(wgts, np.float32)
+    S, M = 0.0, 0
+    for a in range(3):
+        s, cnt = _scatter_sums(inds[:, a], np.abs(wgts[:, a][:, None, :] * grad_y), m)
+        S, M = S + s, M + cnt
+    return _bound(S, M)
