@@ -360,6 +360,24 @@ pcr_status pcr_mutual_nn_match(const float *f1, const float *f2, int p, int n1, 
 pcr_status pcr_mutual_nn_match_cm(const float *f1, const float *f2, int p, int n1, int n2, int c,
                                   int *corr12, int *corr21, int *idx1, int *idx2, int *count,
                                   void *workspace, size_t workspace_bytes, void *stream);
+/* The same on ragged pairs: counts1 / counts2 [p] int32 on
+ * the device; pair q's valid rows are the first v1 = counts1[q] of f1 and the
+ * first v2 = counts2[q] of f2, both clamped to [0, n]; a NULL pointer: all n
+ * of that side.  The strides stay n1 / n2 (channel_major != 0: the layout of
+ * pcr_mutual_nn_match_cm).  Pair q's result is that of the dense call on
+ * f1[q, :v1, :], f2[q, :v2, :] -- diff bits, tie order, NaN first -- and a
+ * fixed fill past the counts: corr12[q, i] = -1 for i >= v1 and everywhere
+ * when v2 = 0 (corr21 with the roles swapped); idx1 / idx2 / count: the
+ * mutual pairs among the valid rows in ascending i, then -1.  Whatever the
+ * rows past the counts hold (zeros, NaN, Inf, copies of valid rows) changes
+ * nothing.  Workspace: pcr_mutual_nn_workspace_size bytes, the layout above;
+ * the keys of rows < v1 and columns < v2 are the winning keys, every other
+ * entry is all-ones.  Every output pointer must be non-NULL. */
+pcr_status pcr_mutual_nn_match_ragged(const float *f1, const float *f2, int p, int n1, int n2,
+                                      int c, const int *counts1, const int *counts2,
+                                      int channel_major, int *corr12, int *corr21, int *idx1,
+                                      int *idx2, int *count, void *workspace,
+                                      size_t workspace_bytes, void *stream);
 
 /* ------------------------- rigid transform from the correspondences -------
  * The step after the matching (datasets/deepgmr_mn40.py:165-231
@@ -418,6 +436,20 @@ pcr_status pcr_icp_point_to_point(const float *xyz1, const float *xyz2, int p, i
                                   double rel_fitness, double rel_rmse, double *transform,
                                   int *corr, int *num_corr, double *fitness, double *rmse,
                                   int *iterations, int *status, void *stream);
+/* The same on ragged pairs (counts1 / counts2 as for
+ * pcr_mutual_nn_match_ragged): only the source points i < v1
+ * and the targets j < v2 exist, fitness = M / v1, corr[q, i] = -1 for
+ * i >= v1.  v1 = 0: the transform is the init, M 0, fitness 0, rmse 0,
+ * iterations 0, status 1.  v2 = 0: no target is within reach (the dense rule:
+ * M = 0, status 1, or 2 with max_iters = 0).  Otherwise every output of pair q
+ * is, bit for bit, that of the dense call on the pair trimmed to its counts.
+ * The points past the counts may hold anything. */
+pcr_status pcr_icp_point_to_point_ragged(const float *xyz1, const float *xyz2, int p, int n1,
+                                         int n2, const int *counts1, const int *counts2,
+                                         const double *init, float max_dist, int max_iters,
+                                         double rel_fitness, double rel_rmse, double *transform,
+                                         int *corr, int *num_corr, double *fitness, double *rmse,
+                                         int *iterations, int *status, void *stream);
 
 /* ------------------------------- Fast Global Registration -----------------
  * utils/open3d_func.py:34-75 (register_one_pair with func='fgr': Open3D
@@ -462,6 +494,20 @@ pcr_status pcr_fgr(const float *xyz1, const float *xyz2, int p, int n1, int n2, 
                    int trials_per_corr, int absolute_scale, unsigned seed, double *transform,
                    int *slots, int *num_corr, int *num_trials, double *mu, int *status,
                    void *workspace, size_t workspace_bytes, void *stream);
+/* The same on ragged pairs (counts1 / counts2 as for
+ * pcr_mutual_nn_match_ragged): the centroids, their divisors
+ * and the scale s run over the valid points only, so pair q's result is, bit
+ * for bit, that of the dense call on the pair trimmed to its counts.  The
+ * rest is unchanged: malformed indices are clamped into the strides n1 / n2,
+ * as before.  A pair with K >= 10 and an empty cloud has no scale: status 2. */
+pcr_status pcr_fgr_ragged(const float *xyz1, const float *xyz2, int p, int n1, int n2,
+                          const int *counts1, const int *counts2, const int *idx1,
+                          const int *idx2, const int *count, double max_corr_dist, int iterations,
+                          double division_factor, int decrease_mu, float tuple_scale,
+                          int max_tuples, int trials_per_corr, int absolute_scale, unsigned seed,
+                          double *transform, int *slots, int *num_corr, int *num_trials,
+                          double *mu, int *status, void *workspace, size_t workspace_bytes,
+                          void *stream);
 
 /* ------------------------------- TEASER-style robust registration ---------
  * datasets/modelnet40_registration.py:274-327 (register_one_pair with
@@ -663,6 +709,24 @@ pcr_status pcr_three_nn_interpolate_backward(const float *grad_y, const int *ind
  * Arithmetic: pcr_estimate_normal of include/pcr_math.h, in fp64. */
 pcr_status pcr_estimate_normals(const float *points, int b, int n, double radius, float *normals,
                                 int *counts, void *stream);
+/* Normals from ready neighbour lists: Open3D's estimate_normals with
+ * KDTreeSearchParamHybrid(radius, max_nn), the search being pcr_hybrid_search
+ * (DESIGN.md 4.8h).  xyz [b,3,n]; nbr_idx [b,k,n] slot-major as
+ * pcr_hybrid_search writes it, the point itself in its own row.  The
+ * neighbours of point i are its slots s = 0 .. k-1 in ascending s whose index
+ * j satisfies 0 <= j < n; any other value (-1, out of range) is skipped and
+ * never used as an address.  The nine cumulants {sx, sy, sz, sxx, sxy, sxz,
+ * syy, syz, szz} are fp64 sums from 0.0 in that order of fp64 products of the
+ * widened coordinates, uncontracted; the normal is pcr_estimate_normal of
+ * include/pcr_math.h on them: (0,0,1) with fewer than 3 neighbours, facing
+ * the origin, unit, rounded to float.  normals [b,3,n]; nbr_count [b,n] (may
+ * be NULL): the slots counted.  Every element is written; a point with an
+ * empty row -- every pad of a ragged cloud -- gets (0,0,1) and 0.  A row that
+ * names a non-finite point may give any normal for that point alone.
+ * n >= 1, 1 <= k <= 128, b * k * n < 2^31; b = 0 returns PCR_OK.  No
+ * workspace, no host sync; bit-identical from run to run. */
+pcr_status pcr_normals_from_neighbors(const float *xyz, const int *nbr_idx, int b, int n, int k,
+                                      float *normals, int *nbr_count, void *stream);
 
 /* ----------------------------------------- on-disk point rows (8f f3) ----
  * datasets/modelnet40.py:30 np.loadtxt(<sample>.txt, delimiter=',') for the

@@ -68,6 +68,22 @@ inline bool with_kmax(int k, F&& f) {
 // ---------------------------------------------------------------- device
 constexpr int kWave = 64;
 
+// Ragged pairs: a kernel template takes a trailing parameter
+// pack that is empty in the dense instantiation -- whose signature and code
+// are then exactly those of the kernel without it -- and one RaggedCounts in
+// the ragged one.  ragged_valid(q, v1, v2, pack...) leaves v1 / v2 (the
+// strides on entry) alone for the empty pack and clamps them to pair q's
+// counts otherwise (a NULL pointer: all of the stride).
+struct RaggedCounts {
+  const int* c1;
+  const int* c2;
+};
+__device__ inline void ragged_valid(int, int&, int&) {}
+__device__ inline void ragged_valid(int q, int& v1, int& v2, RaggedCounts rc) {
+  if (rc.c1) v1 = min(max(rc.c1[q], 0), v1);
+  if (rc.c2) v2 = min(max(rc.c2[q], 0), v2);
+}
+
 // Diagnostic phase stamps (separate build, -DPCR_DIAG, lib/libpcr_amd_diag.so):
 // lane 0 of wave 0 of workgroup g records s_memtime at phase p into
 // pcr_diag_stamps[g][p]; read back with pcr_diag_read().  Compiled out of the

@@ -131,12 +131,18 @@ __device__ inline double fgr_block_max(double v, double (*red_s)[16]) {
   return v;
 }
 
+// RG: the ragged pack of common.hpp.  The centroids, their
+// divisors and the scale run over the valid points v1 / v2; pcr_fgr_sum's
+// order depends on the index alone, so a pair gives the bits of the dense
+// kernel on the pair trimmed to its counts.  An empty cloud has no scale:
+// status 2.
+template <typename... RG>
 __global__ __launch_bounds__(kFT) void fgr_gnc_kernel(
     const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n1, int n2,
     const float* __restrict__ pts, const int* __restrict__ num_corr, int kcap, int cap,
     double max_corr_dist, int iterations, double division_factor, int decrease_mu,
     int absolute_scale, double* __restrict__ transform, double* __restrict__ mu_out,
-    int* __restrict__ status) {
+    int* __restrict__ status, RG... rg) {
   extern __shared__ __attribute__((aligned(16))) char fgr_smem[];
   double* pq_s = (double*)fgr_smem;  // [6][cap]: p x y z, q0 x y z
   double(*red_s)[16] = (double(*)[16])(pq_s + (size_t)6 * cap);
@@ -147,6 +153,8 @@ __global__ __launch_bounds__(kFT) void fgr_gnc_kernel(
   double* tq = transform + (size_t)q * 16;
   const int K = num_corr[q];
   const bool resident = K <= cap;
+  int v1 = n1, v2 = n2;
+  ragged_valid(q, v1, v2, rg...);
 
   double m1[3], m2[3], s = 0.0;
   int st = 0;
@@ -155,26 +163,27 @@ __global__ __launch_bounds__(kFT) void fgr_gnc_kernel(
   } else {
     // centroids: per-thread sums in ascending i, then the block sum
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = tid; i < n1; i += kFT) {
+    for (int i = tid; i < v1; i += kFT) {
 #pragma unroll
       for (int d = 0; d < 3; d++) acc[d] += (double)A[(size_t)d * n1 + i];
     }
-    for (int i = tid; i < n2; i += kFT) {
+    for (int i = tid; i < v2; i += kFT) {
 #pragma unroll
       for (int d = 0; d < 3; d++) acc[3 + d] += (double)B[(size_t)d * n2 + i];
     }
     block_sum_d<kFW>(acc, red_s);
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-      m1[d] = acc[d] / (double)n1;
-      m2[d] = acc[3 + d] / (double)n2;
+      m1[d] = acc[d] / (double)v1;
+      m2[d] = acc[3 + d] / (double)v2;
     }
-    for (int i = tid; i < n1; i += kFT)
+    for (int i = tid; i < v1; i += kFT)
       s = fgr_max(s, pcr_fgr_norm(A[i], A[(size_t)n1 + i], A[(size_t)2 * n1 + i], m1));
-    for (int i = tid; i < n2; i += kFT)
+    for (int i = tid; i < v2; i += kFT)
       s = fgr_max(s, pcr_fgr_norm(B[i], B[(size_t)n2 + i], B[(size_t)2 * n2 + i], m2));
     s = fgr_block_max(s, red_s);
     if (!(s > 0.0 && s < __builtin_inf())) st = 2;  // uniform: the same bits in every thread
+    if (sizeof...(RG) != 0 && (v1 == 0 || v2 == 0)) st = 2;
   }
   if (st) {
     if (tid < 16) tq[tid] = (tid % 5 == 0) ? 1.0 : 0.0;
@@ -266,14 +275,15 @@ extern "C" size_t pcr_fgr_workspace_size(int p, int n1, int max_tuples) {
   return fgr_ws_bytes(p, fgr_kcap(n1, max_tuples));
 }
 
-extern "C" pcr_status pcr_fgr(const float* xyz1, const float* xyz2, int p, int n1, int n2,
-                              const int* idx1, const int* idx2, const int* count,
-                              double max_corr_dist, int iterations, double division_factor,
-                              int decrease_mu, float tuple_scale, int max_tuples,
-                              int trials_per_corr, int absolute_scale, unsigned seed,
-                              double* transform, int* slots, int* num_corr, int* num_trials,
-                              double* mu, int* status, void* workspace, size_t workspace_bytes,
-                              void* stream) {
+// both entry points: counts1 / counts2 are read only when `ragged`
+static pcr_status fgr_run(bool ragged, const float* xyz1, const float* xyz2, int p, int n1, int n2,
+                          const int* counts1, const int* counts2, const int* idx1,
+                          const int* idx2, const int* count, double max_corr_dist, int iterations,
+                          double division_factor, int decrease_mu, float tuple_scale,
+                          int max_tuples, int trials_per_corr, int absolute_scale, unsigned seed,
+                          double* transform, int* slots, int* num_corr, int* num_trials,
+                          double* mu, int* status, void* workspace, size_t workspace_bytes,
+                          void* stream) {
   PCR_REQUIRE(p >= 0 && n1 >= 1 && n2 >= 1, "fgr: invalid sizes");
   PCR_REQUIRE(iterations >= 0 && iterations <= PCR_FGR_MAX_ITERS,
               "fgr: iterations (%d) outside [0, %d]", iterations, PCR_FGR_MAX_ITERS);
@@ -300,9 +310,46 @@ extern "C" pcr_status pcr_fgr(const float* xyz1, const float* xyz2, int p, int n
                      num_trials, pts);
   const int cap = min(kcap, kFCap);
   const size_t lds = fgr_lds_bytes(cap);
-  allow_big_lds(fgr_gnc_kernel, lds);
-  hipLaunchKernelGGL(fgr_gnc_kernel, dim3(p), dim3(kFT), lds, st, xyz1, xyz2, n1, n2, pts,
-                     num_corr, kcap, cap, max_corr_dist, iterations, division_factor, decrease_mu,
-                     absolute_scale, transform, mu, status);
+  if (ragged) {
+    const RaggedCounts rc = {counts1, counts2};
+    allow_big_lds(fgr_gnc_kernel<RaggedCounts>, lds);
+    hipLaunchKernelGGL(fgr_gnc_kernel<RaggedCounts>, dim3(p), dim3(kFT), lds, st, xyz1, xyz2, n1,
+                       n2, pts, num_corr, kcap, cap, max_corr_dist, iterations, division_factor,
+                       decrease_mu, absolute_scale, transform, mu, status, rc);
+  } else {
+    allow_big_lds(fgr_gnc_kernel<>, lds);
+    hipLaunchKernelGGL(fgr_gnc_kernel<>, dim3(p), dim3(kFT), lds, st, xyz1, xyz2, n1, n2, pts,
+                       num_corr, kcap, cap, max_corr_dist, iterations, division_factor, decrease_mu,
+                       absolute_scale, transform, mu, status);
+  }
   return launch_status("fgr");
+}
+
+extern "C" pcr_status pcr_fgr(const float* xyz1, const float* xyz2, int p, int n1, int n2,
+                              const int* idx1, const int* idx2, const int* count,
+                              double max_corr_dist, int iterations, double division_factor,
+                              int decrease_mu, float tuple_scale, int max_tuples,
+                              int trials_per_corr, int absolute_scale, unsigned seed,
+                              double* transform, int* slots, int* num_corr, int* num_trials,
+                              double* mu, int* status, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  return fgr_run(false, xyz1, xyz2, p, n1, n2, nullptr, nullptr, idx1, idx2, count, max_corr_dist,
+                 iterations, division_factor, decrease_mu, tuple_scale, max_tuples,
+                 trials_per_corr, absolute_scale, seed, transform, slots, num_corr, num_trials, mu,
+                 status, workspace, workspace_bytes, stream);
+}
+
+extern "C" pcr_status pcr_fgr_ragged(const float* xyz1, const float* xyz2, int p, int n1, int n2,
+                                     const int* counts1, const int* counts2, const int* idx1,
+                                     const int* idx2, const int* count, double max_corr_dist,
+                                     int iterations, double division_factor, int decrease_mu,
+                                     float tuple_scale, int max_tuples, int trials_per_corr,
+                                     int absolute_scale, unsigned seed, double* transform,
+                                     int* slots, int* num_corr, int* num_trials, double* mu,
+                                     int* status, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  return fgr_run(true, xyz1, xyz2, p, n1, n2, counts1, counts2, idx1, idx2, count, max_corr_dist,
+                 iterations, division_factor, decrease_mu, tuple_scale, max_tuples,
+                 trials_per_corr, absolute_scale, seed, transform, slots, num_corr, num_trials, mu,
+                 status, workspace, workspace_bytes, stream);
 }

@@ -23,6 +23,12 @@
 //     target and its coordinates stay in registers between the evaluation
 //     and the covariance pass, and corr is written once at the end; larger
 //     n1 keeps the nearest index in corr and re-reads the points.
+//     Ragged pairs (the RG pack of common.hpp): the valid
+//     lengths v1 / v2 bound the points and the targets, the strides n1 / n2
+//     choose the paths.  The thread that owns point i, the order of its sums
+//     and the ascending strict-`<` target scan depend on i and j alone, so a
+//     pair gives the bits of the dense kernel on the pair trimmed to v1 / v2
+//     whichever path either takes.
 #include "common.hpp"
 #include "pcr_rigid.h"
 #include "rigid_pair.hpp"
@@ -93,13 +99,13 @@ __device__ inline void icp_scan(const float* tg, int cap, int c0, int len,
   }
 }
 
-template <bool kResident>
+template <bool kResident, typename... RG>
 __global__ __launch_bounds__(kIT) void icp_kernel(
     const float* __restrict__ xyz1, const float* __restrict__ xyz2, int n1, int n2,
     const double* __restrict__ init, float tau2, int max_iters, double rel_fitness,
     double rel_rmse, int cap, double* __restrict__ transform, int* __restrict__ corr,
     int* __restrict__ num_corr, double* __restrict__ fitness, double* __restrict__ rmse,
-    int* __restrict__ iterations, int* __restrict__ status) {
+    int* __restrict__ iterations, int* __restrict__ status, RG... rg) {
   extern __shared__ __attribute__((aligned(16))) char icp_smem[];
   float* tg = (float*)icp_smem;  // [3][cap]
   double(*red_s)[16] = (double(*)[16])(icp_smem + (size_t)cap * 12);
@@ -108,8 +114,15 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
   const float* A = xyz1 + (size_t)q * 3 * n1;
   const float* B = xyz2 + (size_t)q * 3 * n2;
   int* cq = corr + (size_t)q * n1;
+  int v1 = n1, v2 = n2;
+  ragged_valid(q, v1, v2, rg...);
+  // an empty source: no evaluation, the init comes back with status 1
+  const bool empty = sizeof...(RG) != 0 && v1 == 0;
   const bool whole = n2 <= cap;  // the target stays in LDS
-  const int tiles = kResident ? 1 : (n1 + kITile - 1) / kITile;
+  const int tiles = kResident ? 1 : (v1 + kITile - 1) / kITile;
+  if (sizeof...(RG) != 0 && (!kResident || empty)) {  // corr past the source's points
+    for (int i = v1 + tid; i < n1; i += kIT) cq[i] = -1;
+  }
 
   double R[9], t[3];
   float T[12];
@@ -122,7 +135,7 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
   }
   pcr_rigid_round(R, t, T);
   if (whole) {
-    icp_stage(tg, cap, B, n2, 0, n2);
+    icp_stage(tg, cap, B, n2, 0, v2);
     lds_barrier();
   }
 
@@ -130,8 +143,12 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
   float a[kIP][3], b[kIP][3];
   int bj[kIP];
   double M = 0.0, E = 0.0, pfit = 0.0, prmse = 0.0;
-  int it = 0, st = 2;
-  for (;; it++) {  // at most max_iters + 1 evaluations
+  int it = 0, st = empty ? 1 : 2;
+  if (empty) {
+#pragma unroll
+    for (int k = 0; k < kIP; k++) bj[k] = -1;
+  }
+  for (; !empty; it++) {  // at most max_iters + 1 evaluations
     // ---- Evaluate(T): nearest targets, M, E and the centroid sums
     double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int tile = 0; tile < tiles; tile++) {
@@ -140,7 +157,7 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
 #pragma unroll
       for (int k = 0; k < kIP; k++) {
         const int i = s0 + k * kIT + tid;
-        if (i < n1) {
+        if (i < v1) {
 #pragma unroll
           for (int d = 0; d < 3; d++) a[k][d] = A[(size_t)d * n1 + i];
           pcr_rigid_apply(T, a[k][0], a[k][1], a[k][2], m[k]);
@@ -151,12 +168,12 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
         bd[k] = __builtin_inff();
         bj[k] = -1;
       }
-      const bool any = s0 + tid < n1;  // k = 0 is the thread's lowest point
+      const bool any = s0 + tid < v1;  // k = 0 is the thread's lowest point
       if (whole) {
-        if (any) icp_scan(tg, cap, 0, n2, m, bd, bj);
+        if (any) icp_scan(tg, cap, 0, v2, m, bd, bj);
       } else {
-        for (int c0 = 0; c0 < n2; c0 += cap) {
-          const int len = min(cap, n2 - c0);
+        for (int c0 = 0; c0 < v2; c0 += cap) {
+          const int len = min(cap, v2 - c0);
           lds_barrier();
           icp_stage(tg, cap, B, n2, c0, len);
           lds_barrier();
@@ -179,13 +196,13 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
             acc[5 + d] += (double)b[k][d];
           }
         }
-        if (!kResident && i < n1) cq[i] = bj[k];
+        if (!kResident && i < v1) cq[i] = bj[k];
       }
     }
     block_sum_d<kIW>(acc, red_s);
     M = acc[0];
     E = acc[1];
-    const double fit = M / (double)n1;
+    const double fit = M / (double)v1;
     const double rm = M > 0.0 ? __builtin_sqrt(E / M) : 0.0;
     const bool conv = it > 0 && __builtin_fabs(pfit - fit) < rel_fitness &&
                       __builtin_fabs(prmse - rm) < rel_rmse;
@@ -215,7 +232,7 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
       for (int k = 0; k < kIP; k++) {
         if (!kResident) {
           const int i = tile * kITile + k * kIT + tid;
-          bj[k] = i < n1 ? cq[i] : -1;  // this thread's own store
+          bj[k] = i < v1 ? cq[i] : -1;  // this thread's own store
           if (bj[k] >= 0) {
 #pragma unroll
             for (int d = 0; d < 3; d++) {
@@ -283,18 +300,26 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
 
 using namespace pcr;
 
-extern "C" pcr_status pcr_icp_point_to_point(const float* xyz1, const float* xyz2, int p, int n1,
-                                             int n2, const double* init, float max_dist,
-                                             int max_iters, double rel_fitness, double rel_rmse,
-                                             double* transform, int* corr, int* num_corr,
-                                             double* fitness, double* rmse, int* iterations,
-                                             int* status, void* stream) {
+// the checks both entry points share
+static pcr_status icp_check(int p, int n1, int n2, float max_dist, int max_iters,
+                            double rel_fitness, double rel_rmse) {
   PCR_REQUIRE(p >= 0 && n1 >= 1 && n2 >= 1, "icp_point_to_point: invalid sizes");
   PCR_REQUIRE(max_dist > 0.0f, "icp_point_to_point: max_dist must be positive");
   PCR_REQUIRE(max_iters >= 0 && max_iters <= kIcpMaxIters,
               "icp_point_to_point: max_iters (%d) outside [0, %d]", max_iters, kIcpMaxIters);
   PCR_REQUIRE(rel_fitness >= 0.0 && rel_rmse >= 0.0,
               "icp_point_to_point: negative or NaN tolerance");
+  return PCR_OK;
+}
+
+extern "C" pcr_status pcr_icp_point_to_point(const float* xyz1, const float* xyz2, int p, int n1,
+                                             int n2, const double* init, float max_dist,
+                                             int max_iters, double rel_fitness, double rel_rmse,
+                                             double* transform, int* corr, int* num_corr,
+                                             double* fitness, double* rmse, int* iterations,
+                                             int* status, void* stream) {
+  if (icp_check(p, n1, n2, max_dist, max_iters, rel_fitness, rel_rmse) != PCR_OK)
+    return PCR_ERR_INVALID;
   if (p == 0) return PCR_OK;
   PCR_REQUIRE(xyz1 && xyz2 && transform && corr && num_corr && fitness && rmse && iterations &&
                   status,
@@ -315,4 +340,35 @@ extern "C" pcr_status pcr_icp_point_to_point(const float* xyz1, const float* xyz
                        fitness, rmse, iterations, status);
   }
   return launch_status("icp_point_to_point");
+}
+
+extern "C" pcr_status pcr_icp_point_to_point_ragged(
+    const float* xyz1, const float* xyz2, int p, int n1, int n2, const int* counts1,
+    const int* counts2, const double* init, float max_dist, int max_iters, double rel_fitness,
+    double rel_rmse, double* transform, int* corr, int* num_corr, double* fitness, double* rmse,
+    int* iterations, int* status, void* stream) {
+  if (icp_check(p, n1, n2, max_dist, max_iters, rel_fitness, rel_rmse) != PCR_OK)
+    return PCR_ERR_INVALID;
+  if (p == 0) return PCR_OK;
+  PCR_REQUIRE(xyz1 && xyz2 && transform && corr && num_corr && fitness && rmse && iterations &&
+                  status,
+              "icp_point_to_point_ragged: null pointer");
+  hipStream_t st = as_stream(stream);
+  // the paths follow the strides; the result does not depend on them
+  const int cap = icp_cap(n2);
+  const size_t lds = icp_lds_bytes(cap);
+  const float tau2 = max_dist * max_dist;
+  const RaggedCounts rc = {counts1, counts2};
+  if (n1 <= kITile) {
+    allow_big_lds(icp_kernel<true, RaggedCounts>, lds);
+    hipLaunchKernelGGL((icp_kernel<true, RaggedCounts>), dim3(p), dim3(kIT), lds, st, xyz1, xyz2,
+                       n1, n2, init, tau2, max_iters, rel_fitness, rel_rmse, cap, transform, corr,
+                       num_corr, fitness, rmse, iterations, status, rc);
+  } else {
+    allow_big_lds(icp_kernel<false, RaggedCounts>, lds);
+    hipLaunchKernelGGL((icp_kernel<false, RaggedCounts>), dim3(p), dim3(kIT), lds, st, xyz1, xyz2,
+                       n1, n2, init, tau2, max_iters, rel_fitness, rel_rmse, cap, transform, corr,
+                       num_corr, fitness, rmse, iterations, status, rc);
+  }
+  return launch_status("icp_point_to_point_ragged");
 }

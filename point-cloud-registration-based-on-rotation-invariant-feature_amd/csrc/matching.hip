@@ -168,15 +168,26 @@ __device__ inline void match_epilogue(const f32x16 (&acc)[2][2], const float (&s
 // after every wave passed the barrier in between).  Three waves per SIMD:
 // the accumulators stay in the unified VGPR file (143 VGPRs, no AGPRs)
 // (DESIGN.md 4.8).
-template <bool CM>
+//
+// RG: empty in the dense instantiations, one RaggedCounts in the ragged ones
+// (common.hpp).  There the pair's valid lengths v1 / v2 take the place of n1 /
+// n2 in the epilogue's tests, so an element of a pad row or column keys as ~0
+// whatever the pad holds (an accumulator element sees its own row and column
+// only), and a workgroup whose tile lies wholly in the pads leaves before its
+// first load; the strides stay n1 / n2.
+template <bool CM, typename... RG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void match_tile_kernel(
     const float* __restrict__ f1, const float* __restrict__ f2, int n1, int n2, int c,
-    unsigned long long* __restrict__ rowbest, unsigned long long* __restrict__ colbest) {
+    unsigned long long* __restrict__ rowbest, unsigned long long* __restrict__ colbest, RG... rg) {
   __shared__ float a_s[2][kKC][kMPad];  // [buf][k][i]
   __shared__ float b_s[2][kKC][kMPad];  // [buf][k][j]
   __shared__ float sq_s[2][kMT];        // the tile's row / column norms
   const int p = blockIdx.z;
   const int i0 = blockIdx.y * kMT, j0 = blockIdx.x * kMT;
+  int v1 = n1, v2 = n2;
+  ragged_valid(p, v1, v2, rg...);
+  // workgroup-uniform, before any barrier
+  if (sizeof...(RG) != 0 && (i0 >= v1 || j0 >= v2)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wi = wv >> 1, wj = wv & 1;  // 2 x 2 waves, 64 x 64 each
   // the norms the epilogue reads: thread t runs pcr_match_sqnorm's ordered
@@ -242,7 +253,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void m
   }
   lds_barrier();
   // epilogue: C/D layout col = lane & 31, row = (v & 3) + 8 (v >> 2) + 4 (lane >> 5)
-  match_epilogue(acc, sq_s, i0, j0, wi, wj, lane, n1, n2, rowbest + (size_t)p * n1,
+  match_epilogue(acc, sq_s, i0, j0, wi, wj, lane, v1, v2, rowbest + (size_t)p * n1,
                  colbest + (size_t)p * n2);
 }
 
@@ -310,12 +321,15 @@ extern "C" size_t pcr_mutual_nn_workspace_size(int p, int n1, int n2) {
 }
 
 static pcr_status mutual_nn(bool cm, const float* f1, const float* f2, int p, int n1, int n2,
-                            int c, int* corr12, int* corr21, int* idx1, int* idx2, int* count,
+                            int c, bool ragged, const int* counts1, const int* counts2,
+                            int* corr12, int* corr21, int* idx1, int* idx2, int* count,
                             void* workspace, size_t workspace_bytes, void* stream,
                             const char* name) {
   PCR_REQUIRE(p >= 0 && n1 >= 1 && n2 >= 1 && c >= 1, "%s: invalid sizes", name);
   PCR_REQUIRE(p <= 65535, "%s: too many pairs (%d)", name, p);
   if (p == 0) return PCR_OK;
+  PCR_REQUIRE(!ragged || (f1 && f2 && corr12 && corr21 && idx1 && idx2 && count),
+              "%s: null pointer", name);
   unsigned long long *rb, *cb;
   const size_t need = match_ws_layout(p, n1, n2, &rb, &cb, (char*)workspace);
   PCR_REQUIRE(workspace != nullptr && workspace_bytes >= need,
@@ -326,7 +340,17 @@ static pcr_status mutual_nn(bool cm, const float* f1, const float* f2, int p, in
       hipSuccess)
     return launch_status(name);
   const dim3 grid(ceil_div(n2, kMT), ceil_div(n1, kMT), p);
-  if (cm)
+  if (ragged) {
+    // the finalize needs no counts: a row or column nothing was merged into
+    // keeps its all-ones key, which reads as -1 and is never mutual
+    const RaggedCounts rc = {counts1, counts2};
+    if (cm)
+      hipLaunchKernelGGL((match_tile_kernel<true, RaggedCounts>), grid, dim3(256), 0, st, f1, f2,
+                         n1, n2, c, rb, cb, rc);
+    else
+      hipLaunchKernelGGL((match_tile_kernel<false, RaggedCounts>), grid, dim3(256), 0, st, f1, f2,
+                         n1, n2, c, rb, cb, rc);
+  } else if (cm)
     hipLaunchKernelGGL(match_tile_kernel<true>, grid, dim3(256), 0, st, f1, f2, n1, n2, c, rb, cb);
   else
     hipLaunchKernelGGL(match_tile_kernel<false>, grid, dim3(256), 0, st, f1, f2, n1, n2, c, rb, cb);
@@ -339,14 +363,25 @@ extern "C" pcr_status pcr_mutual_nn_match(const float* f1, const float* f2, int 
                                           int c, int* corr12, int* corr21, int* idx1, int* idx2,
                                           int* count, void* workspace, size_t workspace_bytes,
                                           void* stream) {
-  return mutual_nn(false, f1, f2, p, n1, n2, c, corr12, corr21, idx1, idx2, count, workspace,
-                   workspace_bytes, stream, "mutual_nn_match");
+  return mutual_nn(false, f1, f2, p, n1, n2, c, false, nullptr, nullptr, corr12, corr21, idx1,
+                   idx2, count, workspace, workspace_bytes, stream, "mutual_nn_match");
 }
 
 extern "C" pcr_status pcr_mutual_nn_match_cm(const float* f1, const float* f2, int p, int n1,
                                              int n2, int c, int* corr12, int* corr21, int* idx1,
                                              int* idx2, int* count, void* workspace,
                                              size_t workspace_bytes, void* stream) {
-  return mutual_nn(true, f1, f2, p, n1, n2, c, corr12, corr21, idx1, idx2, count, workspace,
-                   workspace_bytes, stream, "mutual_nn_match_cm");
+  return mutual_nn(true, f1, f2, p, n1, n2, c, false, nullptr, nullptr, corr12, corr21, idx1,
+                   idx2, count, workspace, workspace_bytes, stream, "mutual_nn_match_cm");
+}
+
+extern "C" pcr_status pcr_mutual_nn_match_ragged(const float* f1, const float* f2, int p, int n1,
+                                                 int n2, int c, const int* counts1,
+                                                 const int* counts2, int channel_major,
+                                                 int* corr12, int* corr21, int* idx1, int* idx2,
+                                                 int* count, void* workspace,
+                                                 size_t workspace_bytes, void* stream) {
+  return mutual_nn(channel_major != 0, f1, f2, p, n1, n2, c, true, counts1, counts2, corr12, corr21,
+                   idx1, idx2, count, workspace, workspace_bytes, stream,
+                   "mutual_nn_match_ragged");
 }

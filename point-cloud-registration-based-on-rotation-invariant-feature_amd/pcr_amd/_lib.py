@@ -73,14 +73,19 @@ SIGNATURES = {
     "pcr_mutual_nn_workspace_size": (SZ, [I, I, I]),
     "pcr_mutual_nn_match": (ST, [P, P, I, I, I, I, P, P, P, P, P, P, SZ, P]),
     "pcr_mutual_nn_match_cm": (ST, [P, P, I, I, I, I, P, P, P, P, P, P, SZ, P]),
+    "pcr_mutual_nn_match_ragged": (ST, [P, P, I, I, I, I, P, P, I, P, P, P, P, P, P, SZ, P]),
     "pcr_rigid_ransac_workspace_size": (SZ, [I, I, I]),
     "pcr_rigid_ransac": (ST, [P, P, I, I, I, P, P, P, I, F, F, I, ctypes.c_uint, P, P, P, P, P, P,
                              P, SZ, P]),
     "pcr_icp_point_to_point": (ST, [P, P, I, I, I, P, F, I, ctypes.c_double, ctypes.c_double, P, P,
                                    P, P, P, P, P, P]),
+    "pcr_icp_point_to_point_ragged": (ST, [P, P, I, I, I, P, P, P, F, I, ctypes.c_double,
+                                          ctypes.c_double, P, P, P, P, P, P, P, P]),
     "pcr_fgr_workspace_size": (SZ, [I, I, I]),
     "pcr_fgr": (ST, [P, P, I, I, I, P, P, P, ctypes.c_double, I, ctypes.c_double, I, F, I, I, I,
                     ctypes.c_uint, P, P, P, P, P, P, P, SZ, P]),
+    "pcr_fgr_ragged": (ST, [P, P, I, I, I, P, P, P, P, P, ctypes.c_double, I, ctypes.c_double, I, F,
+                           I, I, I, ctypes.c_uint, P, P, P, P, P, P, P, SZ, P]),
     "pcr_teaser_workspace_size": (SZ, [I, I]),
     "pcr_teaser": (ST, [P, P, I, I, I, P, P, P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                        I, ctypes.c_double, I, I, P, P, P, P, P, P, P, P, SZ, P]),
@@ -98,6 +103,7 @@ SIGNATURES = {
     "pcr_three_nn_interpolate_forward": (ST, [P, P, P, I, I, I, I, P, P, P, P]),
     "pcr_three_nn_interpolate_backward": (ST, [P, P, P, I, I, I, I, P, P]),
     "pcr_estimate_normals": (ST, [P, I, I, ctypes.c_double, P, P, P]),
+    "pcr_normals_from_neighbors": (ST, [P, P, I, I, I, P, P, P]),
     "pcr_txt_shape": (ST, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong),
                            ctypes.POINTER(ctypes.c_int)]),
     "pcr_read_xyzn_txt": (ST, [ctypes.c_char_p, P, ctypes.c_longlong, I]),

@@ -474,7 +474,52 @@ def estimate_normals(points, radius=0.1, return_counts=False):
     return (normals, counts) if return_counts else normals
 
 
-def mutual_nn_match(feat1, feat2, channel_major=False, workspace=None, return_keys=False):
+def _check_counts(counts, p, what):
+    """counts [p] int32 on the device, or None"""
+    if counts is not None:
+        _check(counts, what, "int")
+        if tuple(counts.shape) != (p,):
+            raise RuntimeError("%s: expected [p] (one count per pair)" % what)
+
+
+def normals_from_neighbors(xyz, nbr_idx, return_counts=False):
+    """Normals from ready neighbour lists (Open3D's estimate_normals with
+    KDTreeSearchParamHybrid, the search taken out): xyz
+    [b, 3, n], nbr_idx [b, k, n] int32 as hybrid_search returns it (the point
+    itself in its own row; k <= 128) -> unit normals [b, 3, n] from the PCA
+    of each row's points, facing the origin, (0, 0, 1) with fewer than 3.  A
+    slot outside [0, n) is skipped, so a point with an empty row -- every pad
+    of a ragged cloud -- gets (0, 0, 1).  return_counts: also the slots
+    counted [b, n] int32.  Bit-identical from run to run."""
+    _check(xyz, "xyz")
+    _check(nbr_idx, "nbr_idx", "int")
+    if xyz.dim() != 3 or xyz.shape[1] != 3 or xyz.shape[2] < 1:
+        raise RuntimeError("normals_from_neighbors: expected xyz [b, 3, n] with n >= 1")
+    b, _, n = xyz.shape
+    if nbr_idx.dim() != 3 or nbr_idx.shape[0] != b or nbr_idx.shape[2] != n:
+        raise RuntimeError("normals_from_neighbors: expected nbr_idx [b, k, n]")
+    k = nbr_idx.shape[1]
+    normals = torch.empty_like(xyz)
+    counts = torch.empty((b, n), dtype=torch.int32, device=xyz.device) if return_counts else None
+    _lib.check(_lib.load().pcr_normals_from_neighbors(
+        _ptr(xyz), _ptr(nbr_idx), b, n, k, _ptr(normals), _ptr(counts), _stream()),
+        "normals_from_neighbors")
+    return (normals, counts) if return_counts else normals
+
+
+def estimate_normals_hybrid(xyz, radius, k=30, counts=None):
+    """Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn=k)) of
+    b ragged clouds: hybrid_search(xyz, radius, min(k, 128), counts), then
+    normals_from_neighbors on its rows.  counts [b] int32 -- cloud q's valid
+    points are its first counts[q] -- or None for all n; the points past them
+    are in no row and get (0, 0, 1)."""
+    k = min(int(k), 128)
+    _, idx, _ = hybrid_search(xyz, radius, k, counts)
+    return normals_from_neighbors(xyz, idx)
+
+
+def mutual_nn_match(feat1, feat2, channel_major=False, workspace=None, return_keys=False,
+                    counts1=None, counts2=None):
     """Feature-space mutual nearest neighbours of p registration pairs
     (datasets/deepgmr_mn40.py:232-244, batched): feat1 [p, n1, c],
     feat2 [p, n2, c] -> (corr12 [p, n1], corr21 [p, n2], idx1 [p, n1],
@@ -484,7 +529,12 @@ def mutual_nn_match(feat1, feat2, channel_major=False, workspace=None, return_ke
     matched in place.  return_keys: also (rowbest [p, n1], colbest [p, n2]),
     the winning 64-bit pcr_match_key of every row / column as int64 views of
     the workspace (the layout include/pcr_amd.h guarantees; no copy, valid
-    until the workspace is reused)."""
+    until the workspace is reused).  counts1 / counts2 [p] int32: ragged pairs
+    (pcr_mutual_nn_match_ragged) -- pair q matches its first
+    counts1[q] rows of feat1 against its first counts2[q] of feat2 and gives
+    the dense result on that trimmed pair, -1 past the counts (keys: all
+    ones); None on one side: all of it.  With both None the dense entry
+    points are called."""
     _check(feat1, "feat1")
     _check(feat2, "feat2")
     if feat1.dim() != 3 or feat2.dim() != 3 or feat1.shape[0] != feat2.shape[0]:
@@ -506,10 +556,18 @@ def mutual_nn_match(feat1, feat2, channel_major=False, workspace=None, return_ke
     need = max(256, lib.pcr_mutual_nn_workspace_size(p, n1, n2))
     ws = workspace if workspace is not None and workspace.numel() >= need else \
         torch.empty(need, dtype=torch.uint8, device=dev)
-    fn = lib.pcr_mutual_nn_match_cm if channel_major else lib.pcr_mutual_nn_match
-    _lib.check(fn(_ptr(feat1), _ptr(feat2), p, n1, n2, c, _ptr(corr12), _ptr(corr21),
-                  _ptr(idx1), _ptr(idx2), _ptr(count), _ptr(ws), ws.numel(), _stream()),
-               "mutual_nn_match")
+    _check_counts(counts1, p, "counts1")
+    _check_counts(counts2, p, "counts2")
+    if counts1 is None and counts2 is None:
+        fn = lib.pcr_mutual_nn_match_cm if channel_major else lib.pcr_mutual_nn_match
+        _lib.check(fn(_ptr(feat1), _ptr(feat2), p, n1, n2, c, _ptr(corr12), _ptr(corr21),
+                      _ptr(idx1), _ptr(idx2), _ptr(count), _ptr(ws), ws.numel(), _stream()),
+                   "mutual_nn_match")
+    else:
+        _lib.check(lib.pcr_mutual_nn_match_ragged(
+            _ptr(feat1), _ptr(feat2), p, n1, n2, c, _ptr(counts1), _ptr(counts2),
+            int(bool(channel_major)), _ptr(corr12), _ptr(corr21), _ptr(idx1), _ptr(idx2),
+            _ptr(count), _ptr(ws), ws.numel(), _stream()), "mutual_nn_match")
     if return_keys:
         off = (p * n1 * 8 + 255) // 256 * 256
         rowbest = ws[:p * n1 * 8].view(torch.int64).view(p, n1)
@@ -570,7 +628,8 @@ def rigid_ransac(xyz1, xyz2, idx1, idx2, count, hyps=1000, inlier_dist=0.08, edg
     return out + (scores,) if return_scores else out
 
 
-def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, rel_rmse=1e-6):
+def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, rel_rmse=1e-6,
+        counts1=None, counts2=None):
     """Point-to-point ICP of p registration pairs (utils/open3d_func.py:63-72,
     register_one_pair(func='icp'), batched; the defaults are its distance 0.2
     and 200 iterations with Open3D's default convergence criteria): xyz1
@@ -579,7 +638,12 @@ def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, re
     [p, n1] nearest target within max_dist or -1, num_corr [p], fitness [p],
     rmse [p], iterations [p], status [p]: 0 converged, 1 fewer than 3
     correspondences, 2 iteration limit).  max_iters = 0 evaluates init.  The
-    whole loop runs on the device; bit-identical from run to run."""
+    whole loop runs on the device; bit-identical from run to run.  counts1 /
+    counts2 [p] int32: ragged pairs (pcr_icp_point_to_point_ragged, DESIGN.md
+    4.8h) -- only the first counts1[q] sources and counts2[q] targets exist,
+    fitness is over counts1[q], corr is -1 past it, and the result is the
+    dense one on the trimmed pair; an empty source returns init with status
+    1.  With both None the dense entry point is called."""
     _check(xyz1, "xyz1")
     _check(xyz2, "xyz2")
     if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
@@ -598,16 +662,23 @@ def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, re
     corr = torch.empty((p, n1), **i32)
     num_corr, iterations, status = (torch.empty((p,), **i32) for _ in range(3))
     fitness, rmse = torch.empty((p,), **f64), torch.empty((p,), **f64)
-    _lib.check(_lib.load().pcr_icp_point_to_point(
-        _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(init), float(max_dist), int(max_iters),
-        float(rel_fitness), float(rel_rmse), _ptr(transform), _ptr(corr), _ptr(num_corr),
-        _ptr(fitness), _ptr(rmse), _ptr(iterations), _ptr(status), _stream()), "icp")
+    _check_counts(counts1, p, "counts1")
+    _check_counts(counts2, p, "counts2")
+    tail = (_ptr(init), float(max_dist), int(max_iters), float(rel_fitness), float(rel_rmse),
+            _ptr(transform), _ptr(corr), _ptr(num_corr), _ptr(fitness), _ptr(rmse),
+            _ptr(iterations), _ptr(status), _stream())
+    if counts1 is None and counts2 is None:
+        _lib.check(_lib.load().pcr_icp_point_to_point(_ptr(xyz1), _ptr(xyz2), p, n1, n2, *tail),
+                   "icp")
+    else:
+        _lib.check(_lib.load().pcr_icp_point_to_point_ragged(
+            _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(counts1), _ptr(counts2), *tail), "icp")
     return transform, corr, num_corr, fitness, rmse, iterations, status
 
 
 def fgr(xyz1, xyz2, idx1, idx2, count, max_corr_dist=0.08, iterations=64, division_factor=1.4,
         decrease_mu=True, tuple_scale=0.95, max_tuples=1000, trials_per_corr=100,
-        absolute_scale=False, seed=0, workspace=None):
+        absolute_scale=False, seed=0, workspace=None, counts1=None, counts2=None):
     """Fast Global Registration of p registration pairs from their
     correspondences (utils/open3d_func.py:34-75, register_one_pair(func='fgr'),
     batched; the defaults are Open3D's FastGlobalRegistrationOption with the
@@ -619,7 +690,11 @@ def fgr(xyz1, xyz2, idx1, idx2, count, max_corr_dist=0.08, iterations=64, divisi
     themselves with max_tuples = 0) --, num_corr [p] their number, num_trials
     [p], mu [p] fp64 the final line-process parameter, status [p]: 0 ok, 1
     fewer than 10 correspondences kept, 2 degenerate or non-finite clouds, 3 a
-    singular step).  Seeded and bit-identical from run to run."""
+    singular step).  Seeded and bit-identical from run to run.  counts1 /
+    counts2 [p] int32: ragged pairs (pcr_fgr_ragged) -- the
+    centroids and the scale run over the first counts1[q] / counts2[q] points,
+    which gives the dense result on the trimmed pair (an empty cloud: status
+    2).  With both None the dense entry point is called."""
     _check(xyz1, "xyz1")
     _check(xyz2, "xyz2")
     _check(idx1, "idx1", "int")
@@ -646,12 +721,18 @@ def fgr(xyz1, xyz2, idx1, idx2, count, max_corr_dist=0.08, iterations=64, divisi
     need = max(256, lib.pcr_fgr_workspace_size(p, n1, max_tuples))
     ws = workspace if workspace is not None and workspace.numel() >= need else \
         torch.empty(need, dtype=torch.uint8, device=dev)
-    _lib.check(lib.pcr_fgr(
-        _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(idx1), _ptr(idx2), _ptr(count),
-        float(max_corr_dist), int(iterations), float(division_factor), int(bool(decrease_mu)),
-        float(tuple_scale), max_tuples, int(trials_per_corr), int(bool(absolute_scale)),
-        int(seed) & 0xFFFFFFFF, _ptr(transform), _ptr(slots), _ptr(num_corr), _ptr(num_trials),
-        _ptr(mu), _ptr(status), _ptr(ws), ws.numel(), _stream()), "fgr")
+    _check_counts(counts1, p, "counts1")
+    _check_counts(counts2, p, "counts2")
+    tail = (_ptr(idx1), _ptr(idx2), _ptr(count),
+            float(max_corr_dist), int(iterations), float(division_factor), int(bool(decrease_mu)),
+            float(tuple_scale), max_tuples, int(trials_per_corr), int(bool(absolute_scale)),
+            int(seed) & 0xFFFFFFFF, _ptr(transform), _ptr(slots), _ptr(num_corr), _ptr(num_trials),
+            _ptr(mu), _ptr(status), _ptr(ws), ws.numel(), _stream())
+    if counts1 is None and counts2 is None:
+        _lib.check(lib.pcr_fgr(_ptr(xyz1), _ptr(xyz2), p, n1, n2, *tail), "fgr")
+    else:
+        _lib.check(lib.pcr_fgr_ragged(_ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(counts1),
+                                      _ptr(counts2), *tail), "fgr")
     return transform, slots, num_corr, num_trials, mu, status
 
 

@@ -30,6 +30,10 @@ search) is the one meant for mostly wrong matches:
 teaser_pairs, or solver="teaser".  fpfh_pairs needs no extractor and no
 weights: it computes FPFH descriptors (ops.fpfh) from the
 points and normals of both clouds and hands them to register_pairs.
+scan_pairs starts one step earlier, from lists of raw scans of any sizes:
+grid subsampling, normals from the hybrid search's rows, then fpfh_pairs on
+the ragged clouds, whose counts (counts1 / counts2) the
+matching, FGR and ICP take.
 
 The native runner (pcr_extractor_run with match_pairs = P) enqueues the
 matching on each step's voxel queue right after its devox (behind the grid
@@ -140,18 +144,19 @@ class PairExtractor:
 ICP_KEYS = ("transform", "corr", "num_corr", "fitness", "rmse", "iterations", "status")
 
 
-def icp_pairs(xyz1, xyz2, init=None, **icp):
+def icp_pairs(xyz1, xyz2, init=None, counts1=None, counts2=None, **icp):
     """register_one_pair(func='icp') (utils/open3d_func.py:63-72), batched
     and on the device: xyz1 [p, 3, n1], xyz2 [p, 3, n2], init [p, 4, 4]
     float64 or None -> ops.icp's outputs as a dict (transform, corr, num_corr,
-    fitness, rmse, iterations, status); `icp`: its keyword arguments."""
-    return dict(zip(ICP_KEYS, ops.icp(xyz1, xyz2, init, **icp)))
+    fitness, rmse, iterations, status); `icp`: its keyword arguments.
+    counts1 / counts2 [p] int32: ragged pairs, as in ops.icp."""
+    return dict(zip(ICP_KEYS, ops.icp(xyz1, xyz2, init, counts1=counts1, counts2=counts2, **icp)))
 
 
-def _icp_refine(xyz1, xyz2, transform, icp):
+def _icp_refine(xyz1, xyz2, transform, icp, counts1=None, counts2=None):
     """ICP from `transform` (pairs whose RANSAC failed carry the identity)
     -> the icp_* keys"""
-    got = ops.icp(xyz1, xyz2, transform, **icp)
+    got = ops.icp(xyz1, xyz2, transform, counts1=counts1, counts2=counts2, **icp)
     return {"icp_" + k: v for k, v in zip(ICP_KEYS, got)}
 
 
@@ -164,25 +169,29 @@ def _solver(solver):
     return solver
 
 
-def _fgr_solve(xyz1, xyz2, idx1, idx2, count, icp, fgr):
+def _fgr_solve(xyz1, xyz2, idx1, idx2, count, icp, fgr, counts1=None, counts2=None):
     """ops.fgr on a matching's output -> the FGR_KEYS, plus the icp_* keys"""
-    out = dict(zip(FGR_KEYS, ops.fgr(xyz1, xyz2, idx1, idx2, count, **fgr)))
+    out = dict(zip(FGR_KEYS, ops.fgr(xyz1, xyz2, idx1, idx2, count, counts1=counts1,
+                                     counts2=counts2, **fgr)))
     if icp is not None:
-        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp))
+        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp, counts1, counts2))
     return out
 
 
-def fgr_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **fgr):
+def fgr_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, counts1=None,
+              counts2=None, **fgr):
     """register_one_pair(func='fgr') (utils/open3d_func.py:34-75) after
     find_correspondence_one_pair, batched and on the device: the arguments of
     register_pairs -> a dict with the matching (idx1, idx2, count) and
     ops.fgr's outputs (transform, slots, num_corr, num_trials, mu,
     reg_status); `fgr`: its keyword arguments.  icp: a dict of ops.icp keywords
     (may be empty) refines the transform into the icp_* keys, as in
+    register_pairs.  counts1 / counts2 [p] int32: ragged pairs, as in
     register_pairs."""
-    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
+    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major,
+                                                  counts1=counts1, counts2=counts2)
     out = {"idx1": idx1, "idx2": idx2, "count": count}
-    out.update(_fgr_solve(xyz1, xyz2, idx1, idx2, count, icp, fgr))
+    out.update(_fgr_solve(xyz1, xyz2, idx1, idx2, count, icp, fgr, counts1, counts2))
     return out
 
 
@@ -190,15 +199,16 @@ TEASER_KEYS = ("transform", "clique", "clique_size", "inliers", "num_inliers", "
                "reg_status")
 
 
-def _teaser_solve(xyz1, xyz2, idx1, idx2, count, icp, teaser):
+def _teaser_solve(xyz1, xyz2, idx1, idx2, count, icp, teaser, counts1=None, counts2=None):
     """ops.teaser on a matching's output -> the TEASER_KEYS, plus the icp_* keys"""
     out = dict(zip(TEASER_KEYS, ops.teaser(xyz1, xyz2, idx1, idx2, count, **teaser)))
     if icp is not None:
-        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp))
+        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp, counts1, counts2))
     return out
 
 
-def teaser_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **teaser):
+def teaser_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, counts1=None,
+                 counts2=None, **teaser):
     """register_one_pair(func='teaserpp')
     (datasets/modelnet40_registration.py:274-327) after
     find_correspondence_one_pair, batched and on the device: the arguments of
@@ -206,15 +216,17 @@ def teaser_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, **teas
     ops.teaser's outputs (transform, clique, clique_size, inliers, num_inliers,
     iterations, reg_status); `teaser`: its keyword arguments.  icp: a dict of
     ops.icp keywords (may be empty) refines the transform into the icp_* keys,
-    as in register_pairs."""
-    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
+    as in register_pairs.  counts1 / counts2 [p] int32: ragged pairs, as in
+    register_pairs (the solver reads only the points the matching names)."""
+    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major,
+                                                  counts1=counts1, counts2=counts2)
     out = {"idx1": idx1, "idx2": idx2, "count": count}
-    out.update(_teaser_solve(xyz1, xyz2, idx1, idx2, count, icp, teaser))
+    out.update(_teaser_solve(xyz1, xyz2, idx1, idx2, count, icp, teaser, counts1, counts2))
     return out
 
 
 def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, solver="ransac",
-                   **ransac):
+                   counts1=None, counts2=None, **ransac):
     """Pair in, transform out (datasets/deepgmr_mn40.py:165-244,
     find_correspondence_one_pair + register_one_pair(func='ransac'), batched
     and on the device): xyz1 [p, 3, n1], xyz2 [p, 3, n2] and per-point
@@ -227,17 +239,23 @@ def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, solv
     icp_num_corr, icp_fitness, icp_rmse, icp_iterations and icp_status, the
     other keys are unchanged.  solver="fgr": fgr_pairs with the same
     arguments (the keywords are ops.fgr's); solver="teaser": teaser_pairs (the
-    keywords are ops.teaser's)."""
+    keywords are ops.teaser's).  counts1 / counts2 [p] int32: ragged pairs
+     -- pair q's clouds are the first counts1[q] / counts2[q]
+    points; the matching names valid points only (RANSAC and TEASER read no
+    others), and FGR and ICP take the counts themselves.  With both None the
+    dense entry points run."""
     if _solver(solver) != "ransac":
         pairs = fgr_pairs if solver == "fgr" else teaser_pairs
-        return pairs(xyz1, xyz2, feat1, feat2, channel_major=channel_major, icp=icp, **ransac)
-    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major)
+        return pairs(xyz1, xyz2, feat1, feat2, channel_major=channel_major, icp=icp,
+                     counts1=counts1, counts2=counts2, **ransac)
+    _, _, idx1, idx2, count = ops.mutual_nn_match(feat1, feat2, channel_major=channel_major,
+                                                  counts1=counts1, counts2=counts2)
     got = ops.rigid_ransac(xyz1, xyz2, idx1, idx2, count, **ransac)
     out = {"idx1": idx1, "idx2": idx2, "count": count}
     out.update(zip(("transform", "inliers", "num_inliers", "best_hyp", "reg_status", "scores"),
                    got))
     if icp is not None:
-        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp))
+        out.update(_icp_refine(xyz1, xyz2, out["transform"], icp, counts1, counts2))
     return out
 
 
@@ -269,17 +287,55 @@ def alignment_rmse(xyz1, gt, est):
 
 
 def fpfh_pairs(xyz1, normals1, xyz2, normals2, radius, k=100, solver="ransac", icp=None,
-               search="knn", **solver_args):
+               search="knn", counts1=None, counts2=None, **solver_args):
     """Two clouds with normals in, transform out, with nothing trained: the
     FPFH descriptors of both clouds (ops.fpfh with `radius`, `k` and `search`:
     "knn" or "grid", the neighbour search behind the descriptor; DESIGN.md
     4.8f, 4.8g), then register_pairs on them (channel-major, 33 channels) with
     `solver`, `icp` and the solver's keyword arguments.  xyz [p, 3, n] and
     normals [p, 3, n] per side -> register_pairs' dict plus feat1 [p, 33, n1]
-    and feat2 [p, 33, n2]."""
-    feat1 = ops.fpfh(xyz1, normals1, radius, k, search=search)
-    feat2 = ops.fpfh(xyz2, normals2, radius, k, search=search)
+    and feat2 [p, 33, n2].  counts1 / counts2 [p] int32: ragged pairs, carried
+    through the descriptors, the matching, the solver and ICP; they need
+    search="grid"."""
+    if (counts1 is not None or counts2 is not None) and search != "grid":
+        raise RuntimeError("fpfh_pairs: counts need search='grid'")
+    feat1 = ops.fpfh(xyz1, normals1, radius, k, search=search, counts=counts1)
+    feat2 = ops.fpfh(xyz2, normals2, radius, k, search=search, counts=counts2)
     out = register_pairs(xyz1, xyz2, feat1, feat2, channel_major=True, icp=icp, solver=solver,
-                         **solver_args)
+                         counts1=counts1, counts2=counts2, **solver_args)
     out["feat1"], out["feat2"] = feat1, feat2
+    return out
+
+
+def scan_pairs(scans1, scans2, cell, normal_radius=None, normal_k=30, feature_radius=None,
+               feature_k=100, solver="ransac", icp=None, **solver_args):
+    """Raw scan pairs in, transforms out, in one batched pass with nothing
+    trained: scans1 / scans2 are lists of [3, n_i] float32
+    clouds of any sizes (pair q is scans1[q], scans2[q]).  io.pad_clouds ->
+    ops.grid_subsample at `cell` -> ops.estimate_normals_hybrid (radius
+    normal_radius, 2 * cell by default, max_nn normal_k) -> ops.fpfh on the
+    grid (radius feature_radius, 5 * cell by default, feature_k) -> the ragged
+    matching -> `solver` -> the ragged ICP with `icp` (a dict of ops.icp
+    keywords, may be empty; None: none).  The subsampled clouds stay ragged
+    all the way and nothing visits the host between the stages.  Returns
+    register_pairs' dict plus xyz1 / xyz2 [p, 3, n], counts1 / counts2 [p],
+    normals1 / normals2, feat1 / feat2 [p, 33, n] and sub_status1 /
+    sub_status2 [p] (ops.grid_subsample's status)."""
+    from . import io
+    if len(scans1) != len(scans2) or len(scans1) < 1:
+        raise RuntimeError("scan_pairs: expected two lists of equal, non-zero length")
+    cell = float(cell)
+    nr = 2.0 * cell if normal_radius is None else float(normal_radius)
+    fr = 5.0 * cell if feature_radius is None else float(feature_radius)
+    side = []
+    for scans in (scans1, scans2):
+        xyz, cnt = io.pad_clouds(scans)
+        sub = ops.grid_subsample(xyz, cell, counts=cnt)
+        normals = ops.estimate_normals_hybrid(sub["xyz"], nr, normal_k, sub["count"])
+        side.append((sub["xyz"], sub["count"], normals, sub["status"]))
+    (x1, c1, nm1, s1), (x2, c2, nm2, s2) = side
+    out = fpfh_pairs(x1, nm1, x2, nm2, fr, feature_k, solver=solver, icp=icp, search="grid",
+                     counts1=c1, counts2=c2, **solver_args)
+    out.update(xyz1=x1, xyz2=x2, counts1=c1, counts2=c2, normals1=nm1, normals2=nm2,
+               sub_status1=s1, sub_status2=s2)
     return out
