@@ -451,6 +451,50 @@ pcr_status pcr_icp_point_to_point_ragged(const float *xyz1, const float *xyz2, i
                                          int *corr, int *num_corr, double *fitness, double *rmse,
                                          int *iterations, int *status, void *stream);
 
+/* ------------------------------------ point-to-plane ICP ------------------
+ * Open3D's registration_icp with TransformationEstimationPointToPlane, for p
+ * pairs, dense or ragged through one entry point (the scalar
+ * math is include/pcr_icp_plane.h on the Cholesky, delta and compose of
+ * include/pcr_fgr.h, include/pcr_rigid.h and pcr_sumsq3f).
+ *   normals2 [p,3,n2] fp32: the target's normals.  counts1 / counts2 [p]
+ *   int32 on the device, or NULL for all n1 / n2 points, clamped to [0, n] as
+ *   for pcr_icp_point_to_point_ragged: v1 / v2 below.  Every other argument
+ *   is as there.
+ *   Evaluate(T) is the point-to-point one, word for word: T rounded to fp32,
+ *   the fp32 fmaf chain, the nearest target by the fp32 squared distance
+ *   (lowest index on ties, a non-finite distance never wins) within
+ *   max_dist * max_dist, M, fitness = M / v1 and the Euclidean rmse.  The
+ *   normals play no part in it.
+ *   Step: every correspondence (i, j) gives, widened to fp64, the fp32 moved
+ *   point m Evaluate searched with, the target b and the normal n =
+ *   normals2[:, j]; r = ((m0-b0) n0 + (m1-b1) n1) + (m2-b2) n2, J = (m x n, n).
+ *   The 27 sums (the upper triangle of J J^T in row order, then J r; each
+ *   thread its points in ascending order, then the workgroup in a fixed order)
+ *   make A and g; A x = g by pcr_fgr_cholesky_solve, x = -x, and
+ *   T <- Delta(x) T in fp64 with pcr_fgr_delta and pcr_fgr_compose: Open3D's
+ *   TransformVector6dToMatrix4d update.
+ *   Iterate from Evaluate(init), at most max_iters times: stop with status 1
+ *   when M < 6; take a step, and stop with status 3 when the Cholesky meets a
+ *   pivot that is not finite and positive (T stays the last evaluated one);
+ *   Evaluate(T); stop with status 0 when |fitness change| < rel_fitness and
+ *   |rmse change| < rel_rmse.  Status 2: the iteration limit (max_iters = 0:
+ *   a pure evaluation of init).  The M < 6 rule and status 3 are this
+ *   library's: Open3D applies the identity update in both cases and goes on.
+ *   The outputs always describe Evaluate at the reported transform;
+ *   corr[q, i] = -1 for i >= v1.  v1 = 0: the transform is the init, M 0,
+ *   fitness 0, rmse 0, iterations 0, status 1.  v2 = 0: M = 0, status 1 (2
+ *   with max_iters = 0).  Otherwise every output of pair q is, bit for bit,
+ *   that of the call on the pair trimmed to its counts; the points and the
+ *   normals past the counts may hold anything.  A bad pair (far apart, NaN, a
+ *   planar target) never fails the call.
+ * Bit-identical from run to run.  Runs on `stream`; needs no workspace. */
+pcr_status pcr_icp_point_to_plane(const float *xyz1, const float *xyz2, const float *normals2,
+                                  int p, int n1, int n2, const int *counts1, const int *counts2,
+                                  const double *init, float max_dist, int max_iters,
+                                  double rel_fitness, double rel_rmse, double *transform,
+                                  int *corr, int *num_corr, double *fitness, double *rmse,
+                                  int *iterations, int *status, void *stream);
+
 /* ------------------------------- Fast Global Registration -----------------
  * utils/open3d_func.py:34-75 (register_one_pair with func='fgr': Open3D
  * registration_fast_based_on_feature_matching), for p pairs, from the

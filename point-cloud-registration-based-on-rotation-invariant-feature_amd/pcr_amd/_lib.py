@@ -81,6 +81,8 @@ SIGNATURES = {
                                    P, P, P, P, P, P]),
     "pcr_icp_point_to_point_ragged": (ST, [P, P, I, I, I, P, P, P, F, I, ctypes.c_double,
                                           ctypes.c_double, P, P, P, P, P, P, P, P]),
+    "pcr_icp_point_to_plane": (ST, [P, P, P, I, I, I, P, P, P, F, I, ctypes.c_double,
+                                   ctypes.c_double, P, P, P, P, P, P, P, P]),
     "pcr_fgr_workspace_size": (SZ, [I, I, I]),
     "pcr_fgr": (ST, [P, P, I, I, I, P, P, P, ctypes.c_double, I, ctypes.c_double, I, F, I, I, I,
                     ctypes.c_uint, P, P, P, P, P, P, P, SZ, P]),

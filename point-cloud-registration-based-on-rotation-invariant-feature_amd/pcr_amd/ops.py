@@ -629,7 +629,7 @@ def rigid_ransac(xyz1, xyz2, idx1, idx2, count, hyps=1000, inlier_dist=0.08, edg
 
 
 def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, rel_rmse=1e-6,
-        counts1=None, counts2=None):
+        counts1=None, counts2=None, estimation="point_to_point", normals2=None):
     """Point-to-point ICP of p registration pairs (utils/open3d_func.py:63-72,
     register_one_pair(func='icp'), batched; the defaults are its distance 0.2
     and 200 iterations with Open3D's default convergence criteria): xyz1
@@ -643,7 +643,18 @@ def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, re
     4.8h) -- only the first counts1[q] sources and counts2[q] targets exist,
     fitness is over counts1[q], corr is -1 past it, and the result is the
     dense one on the trimmed pair; an empty source returns init with status
-    1.  With both None the dense entry point is called."""
+    1.  With both None the dense entry point is called.
+    estimation="point_to_plane" (pcr_icp_point_to_plane, DESIGN.md 4.8i;
+    Open3D's TransformationEstimationPointToPlane): the same evaluation, but
+    each step is the Gauss-Newton one on the residuals (R a + t - b) . n along
+    the target's normals, normals2 [p, 3, n2] float32 (needed then; counts2
+    covers them too).  Its status 1 is fewer than 6 correspondences, and
+    status 3 a step whose 6 x 6 system has no Cholesky factor (a planar
+    target, a NaN normal): the transform is then the last evaluated one."""
+    if estimation not in ("point_to_point", "point_to_plane"):
+        raise RuntimeError("icp: unknown estimation %r: expected 'point_to_point' or "
+                           "'point_to_plane'" % (estimation,))
+    plane = estimation == "point_to_plane"
     _check(xyz1, "xyz1")
     _check(xyz2, "xyz2")
     if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
@@ -655,6 +666,12 @@ def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, re
         _check(init, "init", None)
         if init.dtype != torch.float64 or tuple(init.shape) != (p, 4, 4):
             raise RuntimeError("icp: init must be a float64 [p, 4, 4] tensor")
+    if plane:
+        if normals2 is None:
+            raise RuntimeError("icp: estimation='point_to_plane' needs normals2")
+        _check(normals2, "normals2")
+        if tuple(normals2.shape) != (p, 3, n2) or normals2.device != xyz2.device:
+            raise RuntimeError("icp: normals2 must be a float [p, 3, n2] tensor on xyz2's device")
     dev = xyz1.device
     i32 = dict(dtype=torch.int32, device=dev)
     f64 = dict(dtype=torch.float64, device=dev)
@@ -667,7 +684,11 @@ def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, re
     tail = (_ptr(init), float(max_dist), int(max_iters), float(rel_fitness), float(rel_rmse),
             _ptr(transform), _ptr(corr), _ptr(num_corr), _ptr(fitness), _ptr(rmse),
             _ptr(iterations), _ptr(status), _stream())
-    if counts1 is None and counts2 is None:
+    if plane:
+        _lib.check(_lib.load().pcr_icp_point_to_plane(
+            _ptr(xyz1), _ptr(xyz2), _ptr(normals2), p, n1, n2, _ptr(counts1), _ptr(counts2),
+            *tail), "icp")
+    elif counts1 is None and counts2 is None:
         _lib.check(_lib.load().pcr_icp_point_to_point(_ptr(xyz1), _ptr(xyz2), p, n1, n2, *tail),
                    "icp")
     else:

@@ -22,7 +22,10 @@ PairExtractor.register, or register_pairs for features from elsewhere;
 rre_rte and alignment_rmse are the reference's error meters.  ops.icp (the
 reference's func='icp' solver) re-fits a transform over every
 point within a distance: icp_pairs on its own, or `icp=` of register /
-register_pairs as the refinement of the RANSAC estimate.  ops.fgr (the
+register_pairs as the refinement of the RANSAC estimate;
+icp=dict(estimation="point_to_plane") refines along the target's normals
+instead, which register, fpfh_pairs and scan_pairs fill in
+from the normals they hold.  ops.fgr (the
 reference's func='fgr' solver) is the other estimate from the
 correspondences: fgr_pairs, or solver="fgr" of register / register_pairs.
 ops.teaser (the reference's func='teaserpp' solver with a bounded clique
@@ -124,11 +127,13 @@ class PairExtractor:
         (target ~ R source + t), inliers, num_inliers, best_hyp and
         reg_status.  icp: a dict of ops.icp keywords (may be empty) refines
         that transform by point-to-point ICP into the icp_* keys of
-        register_pairs.  solver="fgr": ops.fgr instead (the keywords are
+        register_pairs; with estimation="point_to_plane" and no normals2 in
+        it, the targets' normals (normals[P:]) are the planes.  solver="fgr": ops.fgr instead (the keywords are
         its own), with the keys of fgr_pairs; solver="teaser": ops.teaser,
         with the keys of teaser_pairs."""
         out = self.forward(xyz, normals, features)
         p = self.pairs
+        icp = _icp_with_normals(icp, normals[p:])
         if _solver(solver) != "ransac":
             solve = _fgr_solve if solver == "fgr" else _teaser_solve
             out.update(solve(xyz[:p], xyz[p:], out["idx1"], out["idx2"], out["count"], icp,
@@ -148,19 +153,30 @@ def icp_pairs(xyz1, xyz2, init=None, counts1=None, counts2=None, **icp):
     """register_one_pair(func='icp') (utils/open3d_func.py:63-72), batched
     and on the device: xyz1 [p, 3, n1], xyz2 [p, 3, n2], init [p, 4, 4]
     float64 or None -> ops.icp's outputs as a dict (transform, corr, num_corr,
-    fitness, rmse, iterations, status); `icp`: its keyword arguments.
-    counts1 / counts2 [p] int32: ragged pairs, as in ops.icp."""
+    fitness, rmse, iterations, status); `icp`: its keyword arguments, among
+    them estimation="point_to_plane" with normals2 [p, 3, n2] (DESIGN.md
+    4.8i).  counts1 / counts2 [p] int32: ragged pairs, as in ops.icp."""
     return dict(zip(ICP_KEYS, ops.icp(xyz1, xyz2, init, counts1=counts1, counts2=counts2, **icp)))
 
 
 def _icp_refine(xyz1, xyz2, transform, icp, counts1=None, counts2=None):
     """ICP from `transform` (pairs whose RANSAC failed carry the identity)
-    -> the icp_* keys"""
+    -> the icp_* keys; `icp` carries estimation / normals2 like any other
+    ops.icp keyword"""
     got = ops.icp(xyz1, xyz2, transform, counts1=counts1, counts2=counts2, **icp)
     return {"icp_" + k: v for k, v in zip(ICP_KEYS, got)}
 
 
 FGR_KEYS = ("transform", "slots", "num_corr", "num_trials", "mu", "reg_status")
+
+
+def _icp_with_normals(icp, normals2):
+    """`icp` with normals2 filled from the target normals the caller holds,
+    when it asks for the point-to-plane step and brings none"""
+    if icp is not None and icp.get("estimation") == "point_to_plane" and \
+            icp.get("normals2") is None:
+        icp = dict(icp, normals2=normals2)
+    return icp
 
 
 def _solver(solver):
@@ -237,7 +253,8 @@ def register_pairs(xyz1, xyz2, feat1, feat2, channel_major=False, icp=None, solv
     keywords (may be empty) refines the RANSAC transform by point-to-point
     ICP over every point; its outputs come as icp_transform, icp_corr,
     icp_num_corr, icp_fitness, icp_rmse, icp_iterations and icp_status, the
-    other keys are unchanged.  solver="fgr": fgr_pairs with the same
+    other keys are unchanged (estimation="point_to_plane" and normals2 in the
+    dict: the point-to-plane step).  solver="fgr": fgr_pairs with the same
     arguments (the keywords are ops.fgr's); solver="teaser": teaser_pairs (the
     keywords are ops.teaser's).  counts1 / counts2 [p] int32: ragged pairs
      -- pair q's clouds are the first counts1[q] / counts2[q]
@@ -296,11 +313,13 @@ def fpfh_pairs(xyz1, normals1, xyz2, normals2, radius, k=100, solver="ransac", i
     normals [p, 3, n] per side -> register_pairs' dict plus feat1 [p, 33, n1]
     and feat2 [p, 33, n2].  counts1 / counts2 [p] int32: ragged pairs, carried
     through the descriptors, the matching, the solver and ICP; they need
-    search="grid"."""
+    search="grid".  icp with estimation="point_to_plane" and no normals2 of
+    its own refines along normals2, the target normals given here."""
     if (counts1 is not None or counts2 is not None) and search != "grid":
         raise RuntimeError("fpfh_pairs: counts need search='grid'")
     feat1 = ops.fpfh(xyz1, normals1, radius, k, search=search, counts=counts1)
     feat2 = ops.fpfh(xyz2, normals2, radius, k, search=search, counts=counts2)
+    icp = _icp_with_normals(icp, normals2)
     out = register_pairs(xyz1, xyz2, feat1, feat2, channel_major=True, icp=icp, solver=solver,
                          counts1=counts1, counts2=counts2, **solver_args)
     out["feat1"], out["feat2"] = feat1, feat2
@@ -316,7 +335,8 @@ def scan_pairs(scans1, scans2, cell, normal_radius=None, normal_k=30, feature_ra
     normal_radius, 2 * cell by default, max_nn normal_k) -> ops.fpfh on the
     grid (radius feature_radius, 5 * cell by default, feature_k) -> the ragged
     matching -> `solver` -> the ragged ICP with `icp` (a dict of ops.icp
-    keywords, may be empty; None: none).  The subsampled clouds stay ragged
+    keywords, may be empty; None: none; estimation="point_to_plane" refines
+    along the targets' estimated normals).  The subsampled clouds stay ragged
     all the way and nothing visits the host between the stages.  Returns
     register_pairs' dict plus xyz1 / xyz2 [p, 3, n], counts1 / counts2 [p],
     normals1 / normals2, feat1 / feat2 [p, 33, n] and sub_status1 /
