@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kFT) void fgr_gnc_kernel(
     if (sizeof...(RG) != 0 && (v1 == 0 || v2 == 0)) st = 2;
   }
   if (st) {
-    if (tid < 16) tq[tid] = (tid % 5 == 0) ? 1.0 : 0.0;
+    rigid_store_identity(tq);
     if (tid == 0) {
       mu_out[q] = 0.0;
       status[q] = st;

@@ -4,33 +4,16 @@
 // as the refinement of pcr_rigid_ransac's transform.  The contract is
 // DESIGN.md 4.8b, the scalar math include/pcr_rigid.h + pcr_sumsq3f.
 //
-//   icp_kernel  one workgroup per pair runs the whole iteration loop (bounded
-//     by the uniform max_iters, no host round trip).  The target cloud lies in
-//     LDS as three planes x / y / z padded with NaN to a multiple of kIPad; it
-//     is staged once when it fits one chunk of kIChunk points and re-staged
-//     chunk by chunk otherwise.  A thread owns kIP source points per tile of
-//     kIT * kIP (point i = tile + k * kIT + tid): it moves them by the current
-//     transform and scans the chunk kIPad targets at a time -- their
-//     ds_read_b128 (four targets of one plane, the same address in every lane:
-//     a broadcast) all issued before the first is scored, then independent
-//     distance chains, strict `<` in ascending j, so the lowest index wins a
-//     tie and a NaN never wins.  M, E, the centroid sums
-//     and the centred cross-covariance are per-thread fp64 sums in ascending
-//     point order, a fixed shuffle butterfly, the waves in order (the scheme
-//     of rigid_refit_kernel): no float atomics, the same bits every run.
-//     Wave 0 solves (pcr_rigid_from_cov) and hands R, t to the others through
-//     LDS.  kResident (n1 <= one tile): the source points, their nearest
-//     target and its coordinates stay in registers between the evaluation
-//     and the covariance pass, and corr is written once at the end; larger
-//     n1 keeps the nearest index in corr and re-reads the points.
-//     Ragged pairs (the RG pack of common.hpp): the valid
-//     lengths v1 / v2 bound the points and the targets, the strides n1 / n2
-//     choose the paths.  The thread that owns point i, the order of its sums
-//     and the ascending strict-`<` target scan depend on i and j alone, so a
-//     pair gives the bits of the dense kernel on the pair trimmed to v1 / v2
-//     whichever path either takes.
+//   icp_kernel  the loop of icp_loop.hpp around the Kabsch step: M, E, the
+//     centroid sums and, in a second pass, the centred cross-covariance of
+//     the correspondences; wave 0 solves (pcr_rigid_from_cov).  kResident
+//     (n1 <= one tile): the source points, their nearest target and its
+//     coordinates stay in registers between the evaluation and the
+//     covariance pass, and corr is written once at the end; larger n1 keeps
+//     the nearest index in corr and re-reads the points.  Ragged pairs come
+//     as the RG pack of common.hpp.
 #include "common.hpp"
-#include "icp_scan.hpp"
+#include "icp_loop.hpp"
 #include "pcr_rigid.h"
 #include "rigid_pair.hpp"
 
@@ -43,10 +26,8 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
     double rel_rmse, int cap, double* __restrict__ transform, int* __restrict__ corr,
     int* __restrict__ num_corr, double* __restrict__ fitness, double* __restrict__ rmse,
     int* __restrict__ iterations, int* __restrict__ status, RG... rg) {
-  extern __shared__ __attribute__((aligned(16))) char icp_smem[];
-  float* tg = (float*)icp_smem;  // [3][cap]
-  double(*red_s)[16] = (double(*)[16])(icp_smem + (size_t)cap * 12);
-  double* sol_s = (double*)(red_s + kIW);  // R[9], t[3]
+  const IcpLds L = icp_lds(cap);
+  float* const tg = L.tg;
   const int q = blockIdx.x, tid = threadIdx.x;
   const float* A = xyz1 + (size_t)q * 3 * n1;
   const float* B = xyz2 + (size_t)q * 3 * n2;
@@ -63,13 +44,7 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
 
   double R[9], t[3];
   float T[12];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-      R[3 * i + j] = init ? init[(size_t)q * 16 + 4 * i + j] : (i == j ? 1.0 : 0.0);
-    t[i] = init ? init[(size_t)q * 16 + 4 * i + 3] : 0.0;
-  }
+  icp_start(init, q, R, t);
   pcr_rigid_round(R, t, T);
   if (whole) {
     icp_stage(tg, cap, B, n2, 0, v2);
@@ -79,7 +54,7 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
   // kResident: the tile's points, their nearest target and its coordinates
   float a[kIP][3], b[kIP][3];
   int bj[kIP];
-  double M = 0.0, E = 0.0, pfit = 0.0, prmse = 0.0;
+  double M = 0.0, pfit = 0.0, prmse = 0.0;
   int it = 0, st = empty ? 1 : 2;
   if (empty) {
 #pragma unroll
@@ -105,18 +80,8 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
         bd[k] = __builtin_inff();
         bj[k] = -1;
       }
-      const bool any = s0 + tid < v1;  // k = 0 is the thread's lowest point
-      if (whole) {
-        if (any) icp_scan(tg, cap, 0, v2, m, bd, bj);
-      } else {
-        for (int c0 = 0; c0 < v2; c0 += cap) {
-          const int len = min(cap, v2 - c0);
-          lds_barrier();
-          icp_stage(tg, cap, B, n2, c0, len);
-          lds_barrier();
-          if (any) icp_scan(tg, cap, c0, len, m, bd, bj);
-        }
-      }
+      // k = 0 is the thread's lowest point
+      icp_nearest(tg, cap, whole, B, n2, v2, s0 + tid < v1, m, bd, bj);
 #pragma unroll
       for (int k = 0; k < kIP; k++) {
         const int i = s0 + k * kIT + tid;
@@ -136,23 +101,12 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
         if (!kResident && i < v1) cq[i] = bj[k];
       }
     }
-    block_sum_d<kIW>(acc, red_s);
+    block_sum_d<kIW>(acc, L.red_s);
     M = acc[0];
-    E = acc[1];
-    const double fit = M / (double)v1;
-    const double rm = M > 0.0 ? __builtin_sqrt(E / M) : 0.0;
-    const bool conv = it > 0 && __builtin_fabs(pfit - fit) < rel_fitness &&
-                      __builtin_fabs(prmse - rm) < rel_rmse;
-    pfit = fit;
-    prmse = rm;
-    // every exit is uniform: the sums are the same bits in every thread
-    if (conv) {
-      st = 0;
-      break;
-    }
-    if (it >= max_iters) break;
-    if (M < 3.0) {
-      st = 1;
+    const int end = icp_verdict<3>(M, acc[1], v1, it, max_iters, rel_fitness, rel_rmse, pfit,
+                                   prmse);
+    if (end >= 0) {
+      st = end;
       break;
     }
     // ---- least squares over the correspondences, from the original points
@@ -187,21 +141,13 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
         }
       }
     }
-    block_sum_d<kIW>(cov, red_s);
+    block_sum_d<kIW>(cov, L.red_s);
     if (tid < kWave) {
       pcr_rigid_from_cov(ca, cb, cov, R, t);
-      if (tid == 0) {
-#pragma unroll
-        for (int i = 0; i < 9; i++) sol_s[i] = R[i];
-#pragma unroll
-        for (int i = 0; i < 3; i++) sol_s[9 + i] = t[i];
-      }
+      if (tid == 0) icp_publish(L.sol_s, R, t);
     }
     lds_barrier();
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = sol_s[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) t[i] = sol_s[9 + i];
+    icp_fetch(L.sol_s, R, t);
     pcr_rigid_round(R, t, T);
   }
 
@@ -212,41 +158,35 @@ __global__ __launch_bounds__(kIT) void icp_kernel(
       if (i < n1) cq[i] = bj[k];
     }
   }
-  if (tid == 0) {
-    double* tq = transform + (size_t)q * 16;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      tq[4 * i] = R[3 * i];
-      tq[4 * i + 1] = R[3 * i + 1];
-      tq[4 * i + 2] = R[3 * i + 2];
-      tq[4 * i + 3] = t[i];
-    }
-    tq[12] = 0.0;
-    tq[13] = 0.0;
-    tq[14] = 0.0;
-    tq[15] = 1.0;
-    num_corr[q] = (int)M;
-    fitness[q] = pfit;
-    rmse[q] = prmse;
-    iterations[q] = it;
-    status[q] = st;
-  }
+  if (tid == 0)
+    icp_store(q, R, t, M, pfit, prmse, it, st, transform, num_corr, fitness, rmse, iterations,
+              status);
 }
 
 }  // namespace pcr
 
 using namespace pcr;
 
-// the checks both entry points share
-static pcr_status icp_check(int p, int n1, int n2, float max_dist, int max_iters,
-                            double rel_fitness, double rel_rmse) {
-  PCR_REQUIRE(p >= 0 && n1 >= 1 && n2 >= 1, "icp_point_to_point: invalid sizes");
-  PCR_REQUIRE(max_dist > 0.0f, "icp_point_to_point: max_dist must be positive");
-  PCR_REQUIRE(max_iters >= 0 && max_iters <= kIcpMaxIters,
-              "icp_point_to_point: max_iters (%d) outside [0, %d]", max_iters, kIcpMaxIters);
-  PCR_REQUIRE(rel_fitness >= 0.0 && rel_rmse >= 0.0,
-              "icp_point_to_point: negative or NaN tolerance");
-  return PCR_OK;
+// Both entry points: the checks, then icp_kernel<kResident, RG...> by the
+// stride n1.  The paths follow the strides; the result does not depend on
+// them.
+template <typename... RG>
+static pcr_status icp_run(const char* name, const char* what, const float* xyz1,
+                          const float* xyz2, int p, int n1, int n2, const double* init,
+                          float max_dist, int max_iters, double rel_fitness, double rel_rmse,
+                          double* transform, int* corr, int* num_corr, double* fitness,
+                          double* rmse, int* iterations, int* status, void* stream, RG... rg) {
+  if (icp_check(name, p, n1, n2, max_dist, max_iters, rel_fitness, rel_rmse) != PCR_OK)
+    return PCR_ERR_INVALID;
+  if (p == 0) return PCR_OK;
+  PCR_REQUIRE(xyz1 && xyz2 && transform && corr && num_corr && fitness && rmse && iterations &&
+                  status,
+              "%s: null pointer", what);
+  const auto kernel = n1 <= kITile ? icp_kernel<true, RG...> : icp_kernel<false, RG...>;
+  icp_launch(kernel, p, n2, stream, xyz1, xyz2, n1, n2, init, max_dist * max_dist, max_iters,
+             rel_fitness, rel_rmse, icp_cap(n2), transform, corr, num_corr, fitness, rmse,
+             iterations, status, rg...);
+  return launch_status(what);
 }
 
 extern "C" pcr_status pcr_icp_point_to_point(const float* xyz1, const float* xyz2, int p, int n1,
@@ -255,57 +195,18 @@ extern "C" pcr_status pcr_icp_point_to_point(const float* xyz1, const float* xyz
                                              double* transform, int* corr, int* num_corr,
                                              double* fitness, double* rmse, int* iterations,
                                              int* status, void* stream) {
-  if (icp_check(p, n1, n2, max_dist, max_iters, rel_fitness, rel_rmse) != PCR_OK)
-    return PCR_ERR_INVALID;
-  if (p == 0) return PCR_OK;
-  PCR_REQUIRE(xyz1 && xyz2 && transform && corr && num_corr && fitness && rmse && iterations &&
-                  status,
-              "icp_point_to_point: null pointer");
-  hipStream_t st = as_stream(stream);
-  const int cap = icp_cap(n2);
-  const size_t lds = icp_lds_bytes(cap);
-  const float tau2 = max_dist * max_dist;
-  if (n1 <= kITile) {
-    allow_big_lds(icp_kernel<true>, lds);
-    hipLaunchKernelGGL(icp_kernel<true>, dim3(p), dim3(kIT), lds, st, xyz1, xyz2, n1, n2, init,
-                       tau2, max_iters, rel_fitness, rel_rmse, cap, transform, corr, num_corr,
-                       fitness, rmse, iterations, status);
-  } else {
-    allow_big_lds(icp_kernel<false>, lds);
-    hipLaunchKernelGGL(icp_kernel<false>, dim3(p), dim3(kIT), lds, st, xyz1, xyz2, n1, n2, init,
-                       tau2, max_iters, rel_fitness, rel_rmse, cap, transform, corr, num_corr,
-                       fitness, rmse, iterations, status);
-  }
-  return launch_status("icp_point_to_point");
+  return icp_run("icp_point_to_point", "icp_point_to_point", xyz1, xyz2, p, n1, n2, init,
+                 max_dist, max_iters, rel_fitness, rel_rmse, transform, corr, num_corr, fitness,
+                 rmse, iterations, status, stream);
 }
 
+// the range errors carry the dense entry point's name
 extern "C" pcr_status pcr_icp_point_to_point_ragged(
     const float* xyz1, const float* xyz2, int p, int n1, int n2, const int* counts1,
     const int* counts2, const double* init, float max_dist, int max_iters, double rel_fitness,
     double rel_rmse, double* transform, int* corr, int* num_corr, double* fitness, double* rmse,
     int* iterations, int* status, void* stream) {
-  if (icp_check(p, n1, n2, max_dist, max_iters, rel_fitness, rel_rmse) != PCR_OK)
-    return PCR_ERR_INVALID;
-  if (p == 0) return PCR_OK;
-  PCR_REQUIRE(xyz1 && xyz2 && transform && corr && num_corr && fitness && rmse && iterations &&
-                  status,
-              "icp_point_to_point_ragged: null pointer");
-  hipStream_t st = as_stream(stream);
-  // the paths follow the strides; the result does not depend on them
-  const int cap = icp_cap(n2);
-  const size_t lds = icp_lds_bytes(cap);
-  const float tau2 = max_dist * max_dist;
-  const RaggedCounts rc = {counts1, counts2};
-  if (n1 <= kITile) {
-    allow_big_lds(icp_kernel<true, RaggedCounts>, lds);
-    hipLaunchKernelGGL((icp_kernel<true, RaggedCounts>), dim3(p), dim3(kIT), lds, st, xyz1, xyz2,
-                       n1, n2, init, tau2, max_iters, rel_fitness, rel_rmse, cap, transform, corr,
-                       num_corr, fitness, rmse, iterations, status, rc);
-  } else {
-    allow_big_lds(icp_kernel<false, RaggedCounts>, lds);
-    hipLaunchKernelGGL((icp_kernel<false, RaggedCounts>), dim3(p), dim3(kIT), lds, st, xyz1, xyz2,
-                       n1, n2, init, tau2, max_iters, rel_fitness, rel_rmse, cap, transform, corr,
-                       num_corr, fitness, rmse, iterations, status, rc);
-  }
-  return launch_status("icp_point_to_point_ragged");
+  return icp_run("icp_point_to_point", "icp_point_to_point_ragged", xyz1, xyz2, p, n1, n2, init,
+                 max_dist, max_iters, rel_fitness, rel_rmse, transform, corr, num_corr, fitness,
+                 rmse, iterations, status, stream, RaggedCounts{counts1, counts2});
 }

@@ -4,23 +4,17 @@
 // DESIGN.md 4.8i, the scalar math include/pcr_icp_plane.h (on pcr_fgr.h's
 // Cholesky, delta and compose), pcr_rigid.h and pcr_sumsq3f.
 //
-//   icp_plane_kernel  one workgroup per pair runs the whole iteration loop,
-//     like icp_kernel, with the target planes and the scan of icp_scan.hpp.
-//     One pass per iteration: a thread moves its kIP source points of a tile,
-//     scans the target for their nearest, writes corr, then gathers the
-//     chosen target's three normal components from global memory (the normals
-//     never enter LDS) and adds the point's 27 Gauss-Newton terms to M and E
-//     in the same pass.  The 29 per-thread fp64 sums, in ascending point
-//     order, go through block_sum_d twice (its rows hold 16): the same bits
-//     every run and in every thread.  Wave 0 solves (pcr_icp_plane_step) and
-//     hands R, t and the Cholesky's verdict to the others through LDS.
-//     counts1 / counts2 (either may be NULL) bound the points and the
-//     targets as in 4.8h; the strides only choose whether the target stays in
-//     LDS.  The thread that owns point i, the order of its sums and the
-//     ascending strict-`<` scan depend on i and j alone, so a pair gives the
-//     bits of the call on the pair trimmed to its counts.
+//   icp_plane_kernel  the loop of icp_loop.hpp around the Gauss-Newton step.
+//     One pass per iteration: after the scan a thread writes corr, gathers
+//     the chosen target's three normal components from global memory (the
+//     normals never enter LDS) and adds the point's 27 Gauss-Newton terms to
+//     M and E in the same pass.  The 29 sums go through block_sum_d twice
+//     (its rows hold 16).  Wave 0 solves (pcr_icp_plane_step) and hands the
+//     Cholesky's verdict on with R, t.  counts1 / counts2 (either may be
+//     NULL) bound the points and the targets; the strides only choose whether
+//     the target stays in LDS.
 #include "common.hpp"
-#include "icp_scan.hpp"
+#include "icp_loop.hpp"
 #include "pcr_icp_plane.h"
 #include "rigid_pair.hpp"
 
@@ -54,10 +48,8 @@ __global__ __launch_bounds__(kIT) void icp_plane_kernel(
     double rel_fitness, double rel_rmse, int cap, double* __restrict__ transform,
     int* __restrict__ corr, int* __restrict__ num_corr, double* __restrict__ fitness,
     double* __restrict__ rmse, int* __restrict__ iterations, int* __restrict__ status) {
-  extern __shared__ __attribute__((aligned(16))) char icp_plane_smem[];
-  float* tg = (float*)icp_plane_smem;  // [3][cap]
-  double(*red_s)[16] = (double(*)[16])(icp_plane_smem + (size_t)cap * 12);
-  double* sol_s = (double*)(red_s + kIW);  // R[9], t[3], bad
+  const IcpLds L = icp_lds(cap);
+  float* const tg = L.tg;
   const int q = blockIdx.x, tid = threadIdx.x;
   const float* A = xyz1 + (size_t)q * 3 * n1;
   const float* B = xyz2 + (size_t)q * 3 * n2;
@@ -73,13 +65,7 @@ __global__ __launch_bounds__(kIT) void icp_plane_kernel(
 
   double R[9], t[3];
   float T[12];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-      R[3 * i + j] = init ? init[(size_t)q * 16 + 4 * i + j] : (i == j ? 1.0 : 0.0);
-    t[i] = init ? init[(size_t)q * 16 + 4 * i + 3] : 0.0;
-  }
+  icp_start(init, q, R, t);
   pcr_rigid_round(R, t, T);
   if (whole) {
     icp_stage(tg, cap, B, n2, 0, v2);
@@ -108,18 +94,8 @@ __global__ __launch_bounds__(kIT) void icp_plane_kernel(
         bd[k] = __builtin_inff();
         bj[k] = -1;
       }
-      const bool any = s0 + tid < v1;  // k = 0 is the thread's lowest point
-      if (whole) {
-        if (any) icp_scan(tg, cap, 0, v2, m, bd, bj);
-      } else {
-        for (int c0 = 0; c0 < v2; c0 += cap) {
-          const int len = min(cap, v2 - c0);
-          lds_barrier();
-          icp_stage(tg, cap, B, n2, c0, len);
-          lds_barrier();
-          if (any) icp_scan(tg, cap, c0, len, m, bd, bj);
-        }
-      }
+      // k = 0 is the thread's lowest point
+      icp_nearest(tg, cap, whole, B, n2, v2, s0 + tid < v1, m, bd, bj);
 #pragma unroll
       for (int k = 0; k < kIP; k++) {
         const int i = s0 + k * kIT + tid;
@@ -140,67 +116,30 @@ __global__ __launch_bounds__(kIT) void icp_plane_kernel(
       }
     }
     // M, E and the 27 sums through block_sum_d, kIPRed at a time
-    icp_plane_sum<0>(acc, red_s);
+    icp_plane_sum<0>(acc, L.red_s);
     M = acc[0];
-    const double fit = M / (double)v1;
-    const double rm = M > 0.0 ? __builtin_sqrt(acc[1] / M) : 0.0;
-    const bool conv = it > 0 && __builtin_fabs(pfit - fit) < rel_fitness &&
-                      __builtin_fabs(prmse - rm) < rel_rmse;
-    pfit = fit;
-    prmse = rm;
-    // every exit is uniform: the sums are the same bits in every thread
-    if (conv) {
-      st = 0;
-      break;
-    }
-    if (it >= max_iters) break;
-    if (M < (double)PCR_ICP_PLANE_MIN_CORR) {
-      st = 1;
+    const int end = icp_verdict<PCR_ICP_PLANE_MIN_CORR>(M, acc[1], v1, it, max_iters, rel_fitness,
+                                                        rel_rmse, pfit, prmse);
+    if (end >= 0) {
+      st = end;
       break;
     }
     // ---- the step: wave 0 solves, T stays as evaluated when the pivots fail
     if (tid < kWave) {
       const int bad = pcr_icp_plane_step(acc + 2, R, t);
-      if (tid == 0) {
-#pragma unroll
-        for (int i = 0; i < 9; i++) sol_s[i] = R[i];
-#pragma unroll
-        for (int i = 0; i < 3; i++) sol_s[9 + i] = t[i];
-        sol_s[12] = bad ? 1.0 : 0.0;
-      }
+      if (tid == 0) icp_publish<true>(L.sol_s, R, t, bad);
     }
     lds_barrier();
-    const bool bad = sol_s[12] != 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = sol_s[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) t[i] = sol_s[9 + i];
-    if (bad) {
+    if (icp_fetch<true>(L.sol_s, R, t)) {
       st = 3;
       break;
     }
     pcr_rigid_round(R, t, T);
   }
 
-  if (tid == 0) {
-    double* tq = transform + (size_t)q * 16;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      tq[4 * i] = R[3 * i];
-      tq[4 * i + 1] = R[3 * i + 1];
-      tq[4 * i + 2] = R[3 * i + 2];
-      tq[4 * i + 3] = t[i];
-    }
-    tq[12] = 0.0;
-    tq[13] = 0.0;
-    tq[14] = 0.0;
-    tq[15] = 1.0;
-    num_corr[q] = (int)M;
-    fitness[q] = pfit;
-    rmse[q] = prmse;
-    iterations[q] = it;
-    status[q] = st;
-  }
+  if (tid == 0)
+    icp_store(q, R, t, M, pfit, prmse, it, st, transform, num_corr, fitness, rmse, iterations,
+              status);
 }
 
 }  // namespace pcr
@@ -212,23 +151,15 @@ extern "C" pcr_status pcr_icp_point_to_plane(
     const int* counts1, const int* counts2, const double* init, float max_dist, int max_iters,
     double rel_fitness, double rel_rmse, double* transform, int* corr, int* num_corr,
     double* fitness, double* rmse, int* iterations, int* status, void* stream) {
-  PCR_REQUIRE(p >= 0 && n1 >= 1 && n2 >= 1, "icp_point_to_plane: invalid sizes");
-  PCR_REQUIRE(max_dist > 0.0f, "icp_point_to_plane: max_dist must be positive");
-  PCR_REQUIRE(max_iters >= 0 && max_iters <= kIcpMaxIters,
-              "icp_point_to_plane: max_iters (%d) outside [0, %d]", max_iters, kIcpMaxIters);
-  PCR_REQUIRE(rel_fitness >= 0.0 && rel_rmse >= 0.0,
-              "icp_point_to_plane: negative or NaN tolerance");
+  if (icp_check("icp_point_to_plane", p, n1, n2, max_dist, max_iters, rel_fitness, rel_rmse) !=
+      PCR_OK)
+    return PCR_ERR_INVALID;
   if (p == 0) return PCR_OK;
   PCR_REQUIRE(xyz1 && xyz2 && normals2 && transform && corr && num_corr && fitness && rmse &&
                   iterations && status,
               "icp_point_to_plane: null pointer");
-  hipStream_t st = as_stream(stream);
-  const int cap = icp_cap(n2);
-  const size_t lds = icp_lds_bytes(cap);
-  const float tau2 = max_dist * max_dist;
-  allow_big_lds(icp_plane_kernel, lds);
-  hipLaunchKernelGGL(icp_plane_kernel, dim3(p), dim3(kIT), lds, st, xyz1, xyz2, normals2, n1, n2,
-                     counts1, counts2, init, tau2, max_iters, rel_fitness, rel_rmse, cap, transform,
-                     corr, num_corr, fitness, rmse, iterations, status);
+  icp_launch(icp_plane_kernel, p, n2, stream, xyz1, xyz2, normals2, n1, n2, counts1, counts2, init,
+             max_dist * max_dist, max_iters, rel_fitness, rel_rmse, icp_cap(n2), transform, corr,
+             num_corr, fitness, rmse, iterations, status);
   return launch_status("icp_point_to_plane");
 }

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(kRB) void rigid_refit_kernel(
   }
   if (st) {  // uniform: identity, no inliers
     for (int s = tid; s < n1; s += kRB) inl[s] = 0;
-    if (tid < 16) tq[tid] = (tid % 5 == 0) ? 1.0 : 0.0;
+    rigid_store_identity(tq);
     if (tid == 0) {
       num_inliers[q] = 0;
       best_hyp[q] = -1;
@@ -241,17 +241,7 @@ __global__ __launch_bounds__(kRB) void rigid_refit_kernel(
     num_inliers[q] = tot;
     best_hyp[q] = bh;
     status[q] = 0;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      tq[4 * i] = R[3 * i];
-      tq[4 * i + 1] = R[3 * i + 1];
-      tq[4 * i + 2] = R[3 * i + 2];
-      tq[4 * i + 3] = t[i];
-    }
-    tq[12] = 0.0;
-    tq[13] = 0.0;
-    tq[14] = 0.0;
-    tq[15] = 1.0;
+    rigid_store_transform(tq, R, t);
   }
 }
 

@@ -1,6 +1,6 @@
 // rigid_pair.hpp -- what the registration solvers (rigid.hip, icp.hip,
-// fgr.hip) share: a pair's clouds and correspondence rows as the kernels
-// address them, and the ordered fp64 workgroup sum.
+// fgr.hip, teaser.hip) share: a pair's clouds and correspondence rows as the
+// kernels address them, the 4 x 4 stores and the ordered fp64 workgroup sum.
 #pragma once
 
 #include "common.hpp"
@@ -46,6 +46,28 @@ __device__ inline void rigid_triple_points(const RigidPair& pr, unsigned seed, i
   pcr_rigid_triple(seed, (unsigned)q, (unsigned)h, (unsigned)pr.m, sl);
 #pragma unroll
   for (int k = 0; k < 3; k++) rigid_slot(pr, sl[k], a + 3 * k, b + 3 * k);
+}
+
+// R, t -> the row-major 4 x 4 at tq, last row 0 0 0 1 (one thread)
+__device__ inline void rigid_store_transform(double* tq, const double (&R)[9],
+                                             const double (&t)[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    tq[4 * i] = R[3 * i];
+    tq[4 * i + 1] = R[3 * i + 1];
+    tq[4 * i + 2] = R[3 * i + 2];
+    tq[4 * i + 3] = t[i];
+  }
+  tq[12] = 0.0;
+  tq[13] = 0.0;
+  tq[14] = 0.0;
+  tq[15] = 1.0;
+}
+
+// the identity 4 x 4 at tq (the workgroup's first 16 threads, one entry each)
+__device__ inline void rigid_store_identity(double* tq) {
+  const int tid = threadIdx.x;
+  if (tid < 16) tq[tid] = (tid % 5 == 0) ? 1.0 : 0.0;
 }
 
 // Sum of v[0..N) over the workgroup of NW waves, the same bits in every

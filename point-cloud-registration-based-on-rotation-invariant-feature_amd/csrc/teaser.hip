@@ -299,7 +299,7 @@ __global__ __launch_bounds__(kTST) void teaser_solve_kernel(
   if (tid < PCR_TEASER_MAX_N1 / 32) inl_s[tid] = 0;  // published by the barriers below
   if (K < PCR_TEASER_MIN_CLIQUE) {  // uniform
     for (int s = tid; s < n1; s += kTST) iq[s] = 0;
-    if (tid < 16) tq[tid] = (tid % 5 == 0) ? 1.0 : 0.0;
+    rigid_store_identity(tq);
     if (tid == 0) {
       num_inliers[q] = 0;
       iterations[q] = 0;
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(kTST) void teaser_solve_kernel(
   mx = teaser_block_max(mx, red_s);
   if (!(mx < __builtin_inf())) {  // uniform: the same bits in every thread
     for (int s = tid; s < n1; s += kTST) iq[s] = 0;
-    if (tid < 16) tq[tid] = (tid % 5 == 0) ? 1.0 : 0.0;
+    rigid_store_identity(tq);
     if (tid == 0) {
       num_inliers[q] = 0;
       iterations[q] = 1;

@@ -56,6 +56,44 @@ def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _workspace_or(workspace, nbytes, device):
+    """the caller's workspace if it is big enough, else a fresh one"""
+    need = max(256, nbytes)
+    if workspace is not None and workspace.numel() >= need:
+        return workspace
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _check_counts(counts, p, what, shape_msg=None):
+    """counts [p] int32 on the device, or None"""
+    if counts is not None:
+        _check(counts, what, "int")
+        if tuple(counts.shape) != (p,):
+            raise RuntimeError(shape_msg or "%s: expected [p] (one count per pair)" % what)
+
+
+def _check_pairs(op, xyz1, xyz2, corr=None):
+    """The solvers' common arguments: xyz1 [p, 3, n1] and xyz2 [p, 3, n2], and
+    with corr = (idx1, idx2, count) the correspondence rows idx1 / idx2
+    [p, n1] and count [p] -> p, n1, n2"""
+    _check(xyz1, "xyz1")
+    _check(xyz2, "xyz2")
+    idx1, idx2, count = corr or (None, None, None)
+    if corr:
+        _check(idx1, "idx1", "int")
+        _check(idx2, "idx2", "int")
+        _check(count, "count", "int")
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
+            xyz1.shape[0] != xyz2.shape[0]:
+        raise RuntimeError("%s: expected [p, 3, n] clouds with equal pair counts" % op)
+    p, _, n1 = xyz1.shape
+    n2 = xyz2.shape[2]
+    if corr and (tuple(idx1.shape) != (p, n1) or tuple(idx2.shape) != (p, n1) or
+                 tuple(count.shape) != (p,)):
+        raise RuntimeError("%s: expected idx1 / idx2 [p, n1] and count [p]" % op)
+    return p, n1, n2
+
+
 # ------------------------------------------------------------------ KNN
 def knn_forward_cuda(xyz1, xyz2, k):
     """knn/knn.cpp:6-25 -> [dist1, dist2, idx1, idx2]."""
@@ -474,14 +512,6 @@ def estimate_normals(points, radius=0.1, return_counts=False):
     return (normals, counts) if return_counts else normals
 
 
-def _check_counts(counts, p, what):
-    """counts [p] int32 on the device, or None"""
-    if counts is not None:
-        _check(counts, what, "int")
-        if tuple(counts.shape) != (p,):
-            raise RuntimeError("%s: expected [p] (one count per pair)" % what)
-
-
 def normals_from_neighbors(xyz, nbr_idx, return_counts=False):
     """Normals from ready neighbour lists (Open3D's estimate_normals with
     KDTreeSearchParamHybrid, the search taken out): xyz
@@ -553,9 +583,7 @@ def mutual_nn_match(feat1, feat2, channel_major=False, workspace=None, return_ke
     idx1, idx2 = torch.empty((p, n1), **i32), torch.empty((p, n1), **i32)
     count = torch.empty((p,), **i32)
     lib = _lib.load()
-    need = max(256, lib.pcr_mutual_nn_workspace_size(p, n1, n2))
-    ws = workspace if workspace is not None and workspace.numel() >= need else \
-        torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace_or(workspace, lib.pcr_mutual_nn_workspace_size(p, n1, n2), dev)
     _check_counts(counts1, p, "counts1")
     _check_counts(counts2, p, "counts2")
     if counts1 is None and counts2 is None:
@@ -596,18 +624,7 @@ def rigid_ransac(xyz1, xyz2, idx1, idx2, count, hyps=1000, inlier_dist=0.08, edg
     num_inliers [p], best_hyp [p], status [p]: 0 ok, 1 fewer than 3
     correspondences, 2 every hypothesis rejected), plus scores [p, hyps] with
     return_scores.  Seeded and bit-identical from run to run."""
-    _check(xyz1, "xyz1")
-    _check(xyz2, "xyz2")
-    _check(idx1, "idx1", "int")
-    _check(idx2, "idx2", "int")
-    _check(count, "count", "int")
-    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
-            xyz1.shape[0] != xyz2.shape[0]:
-        raise RuntimeError("rigid_ransac: expected [p, 3, n] clouds with equal pair counts")
-    p, _, n1 = xyz1.shape
-    n2 = xyz2.shape[2]
-    if tuple(idx1.shape) != (p, n1) or tuple(idx2.shape) != (p, n1) or tuple(count.shape) != (p,):
-        raise RuntimeError("rigid_ransac: expected idx1 / idx2 [p, n1] and count [p]")
+    p, n1, n2 = _check_pairs("rigid_ransac", xyz1, xyz2, (idx1, idx2, count))
     hyps, refine_iters = int(hyps), int(refine_iters)
     dev = xyz1.device
     i32 = dict(dtype=torch.int32, device=dev)
@@ -616,9 +633,7 @@ def rigid_ransac(xyz1, xyz2, idx1, idx2, count, hyps=1000, inlier_dist=0.08, edg
     num_inliers, best_hyp, status = (torch.empty((p,), **i32) for _ in range(3))
     scores = torch.empty((p, max(hyps, 0)), **i32) if return_scores else None
     lib = _lib.load()
-    need = max(256, lib.pcr_rigid_ransac_workspace_size(p, n1, hyps))
-    ws = workspace if workspace is not None and workspace.numel() >= need else \
-        torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace_or(workspace, lib.pcr_rigid_ransac_workspace_size(p, n1, hyps), dev)
     _lib.check(lib.pcr_rigid_ransac(
         _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(idx1), _ptr(idx2), _ptr(count), hyps,
         float(inlier_dist), float(edge_ratio), refine_iters, int(seed) & 0xFFFFFFFF,
@@ -655,13 +670,7 @@ def icp(xyz1, xyz2, init=None, max_dist=0.2, max_iters=200, rel_fitness=1e-6, re
         raise RuntimeError("icp: unknown estimation %r: expected 'point_to_point' or "
                            "'point_to_plane'" % (estimation,))
     plane = estimation == "point_to_plane"
-    _check(xyz1, "xyz1")
-    _check(xyz2, "xyz2")
-    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
-            xyz1.shape[0] != xyz2.shape[0]:
-        raise RuntimeError("icp: expected [p, 3, n] clouds with equal pair counts")
-    p, _, n1 = xyz1.shape
-    n2 = xyz2.shape[2]
+    p, n1, n2 = _check_pairs("icp", xyz1, xyz2)
     if init is not None:
         _check(init, "init", None)
         if init.dtype != torch.float64 or tuple(init.shape) != (p, 4, 4):
@@ -716,18 +725,7 @@ def fgr(xyz1, xyz2, idx1, idx2, count, max_corr_dist=0.08, iterations=64, divisi
     centroids and the scale run over the first counts1[q] / counts2[q] points,
     which gives the dense result on the trimmed pair (an empty cloud: status
     2).  With both None the dense entry point is called."""
-    _check(xyz1, "xyz1")
-    _check(xyz2, "xyz2")
-    _check(idx1, "idx1", "int")
-    _check(idx2, "idx2", "int")
-    _check(count, "count", "int")
-    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
-            xyz1.shape[0] != xyz2.shape[0]:
-        raise RuntimeError("fgr: expected [p, 3, n] clouds with equal pair counts")
-    p, _, n1 = xyz1.shape
-    n2 = xyz2.shape[2]
-    if tuple(idx1.shape) != (p, n1) or tuple(idx2.shape) != (p, n1) or tuple(count.shape) != (p,):
-        raise RuntimeError("fgr: expected idx1 / idx2 [p, n1] and count [p]")
+    p, n1, n2 = _check_pairs("fgr", xyz1, xyz2, (idx1, idx2, count))
     max_tuples = int(max_tuples)
     if max_tuples < 0:
         raise RuntimeError("fgr: negative max_tuples (%d)" % max_tuples)
@@ -739,9 +737,7 @@ def fgr(xyz1, xyz2, idx1, idx2, count, max_corr_dist=0.08, iterations=64, divisi
     num_corr, num_trials, status = (torch.empty((p,), **i32) for _ in range(3))
     mu = torch.empty((p,), **f64)
     lib = _lib.load()
-    need = max(256, lib.pcr_fgr_workspace_size(p, n1, max_tuples))
-    ws = workspace if workspace is not None and workspace.numel() >= need else \
-        torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace_or(workspace, lib.pcr_fgr_workspace_size(p, n1, max_tuples), dev)
     _check_counts(counts1, p, "counts1")
     _check_counts(counts2, p, "counts2")
     tail = (_ptr(idx1), _ptr(idx2), _ptr(count),
@@ -772,27 +768,14 @@ def teaser(xyz1, xyz2, idx1, idx2, count, noise_bound=0.02, cbar2=1.0, gnc_facto
     fewer than 3, 2 non-finite points, 3 the iteration limit).  seeds: how many
     of the best-ranked slots start a search (0: all).  n1 <= 4096.
     Bit-identical from run to run."""
-    _check(xyz1, "xyz1")
-    _check(xyz2, "xyz2")
-    _check(idx1, "idx1", "int")
-    _check(idx2, "idx2", "int")
-    _check(count, "count", "int")
-    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3 or \
-            xyz1.shape[0] != xyz2.shape[0]:
-        raise RuntimeError("teaser: expected [p, 3, n] clouds with equal pair counts")
-    p, _, n1 = xyz1.shape
-    n2 = xyz2.shape[2]
-    if tuple(idx1.shape) != (p, n1) or tuple(idx2.shape) != (p, n1) or tuple(count.shape) != (p,):
-        raise RuntimeError("teaser: expected idx1 / idx2 [p, n1] and count [p]")
+    p, n1, n2 = _check_pairs("teaser", xyz1, xyz2, (idx1, idx2, count))
     dev = xyz1.device
     i32 = dict(dtype=torch.int32, device=dev)
     transform = torch.empty((p, 4, 4), dtype=torch.float64, device=dev)
     clique, inliers = torch.empty((p, n1), **i32), torch.empty((p, n1), **i32)
     clique_size, num_inliers, iterations, status = (torch.empty((p,), **i32) for _ in range(4))
     lib = _lib.load()
-    need = max(256, lib.pcr_teaser_workspace_size(p, n1))
-    ws = workspace if workspace is not None and workspace.numel() >= need else \
-        torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace_or(workspace, lib.pcr_teaser_workspace_size(p, n1), dev)
     _lib.check(lib.pcr_teaser(
         _ptr(xyz1), _ptr(xyz2), p, n1, n2, _ptr(idx1), _ptr(idx2), _ptr(count), float(noise_bound),
         float(cbar2), float(gnc_factor), int(max_iters), float(cost_threshold), int(seeds),
@@ -826,10 +809,7 @@ def grid_subsample(xyz, cell, features=None, counts=None):
         if features.dim() != 3 or features.shape[0] != b or features.shape[2] != n:
             raise RuntimeError("grid_subsample: expected features [b, c, n]")
         c = features.shape[1]
-    if counts is not None:
-        _check(counts, "counts", "int")
-        if tuple(counts.shape) != (b,):
-            raise RuntimeError("grid_subsample: expected counts [b]")
+    _check_counts(counts, b, "counts", "grid_subsample: expected counts [b]")
     dev = xyz.device
     i32 = dict(dtype=torch.int32, device=dev)
     f32 = dict(dtype=torch.float32, device=dev)
@@ -931,10 +911,7 @@ def hybrid_search(xyz, radius, k, counts=None, return_within=False):
     k = int(k)
     if k < 1 or k > 128:
         raise RuntimeError("hybrid_search: k must be in [1, 128] (got %d)" % k)
-    if counts is not None:
-        _check(counts, "counts", "int")
-        if tuple(counts.shape) != (b,):
-            raise RuntimeError("hybrid_search: expected counts [b]")
+    _check_counts(counts, b, "counts", "hybrid_search: expected counts [b]")
     dev = xyz.device
     dist = torch.empty((b, k, n), dtype=torch.float32, device=dev)
     idx = torch.empty((b, k, n), dtype=torch.int32, device=dev)

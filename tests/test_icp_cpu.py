@@ -152,6 +152,47 @@ def test_argument_checks_need_no_gpu():
         assert call(**{k: None}) == -1, k
 
 
+# rejected argument -> the message's tail; `{range}` is the name the range
+# checks print, `{null}` the one the pointer check prints
+ICP_ERRORS = (
+    (dict(n1=0), "{range}: invalid sizes"),
+    (dict(dist=0.0), "{range}: max_dist must be positive"),
+    (dict(iters=-1), "{range}: max_iters (-1) outside [0, 100000]"),
+    (dict(iters=100001), "{range}: max_iters (100001) outside [0, 100000]"),
+    (dict(rf=-1e-9), "{range}: negative or NaN tolerance"),
+    (dict(rr=float("nan")), "{range}: negative or NaN tolerance"),
+    (dict(transform=None), "{null}: null pointer"),
+)
+# entry point -> (range name, null name): the ragged entry point reports its
+# range errors under the dense name
+ICP_ENTRY_NAMES = {
+    "pcr_icp_point_to_point": ("icp_point_to_point", "icp_point_to_point"),
+    "pcr_icp_point_to_point_ragged": ("icp_point_to_point", "icp_point_to_point_ragged"),
+    "pcr_icp_point_to_plane": ("icp_point_to_plane", "icp_point_to_plane"),
+}
+
+
+@pytest.mark.parametrize("entry", list(ICP_ENTRY_NAMES))
+def test_error_text_of_every_icp_entry_point(entry):
+    """the three ICP entry points share one range check: each rejected
+    argument leaves exactly the text the entry point gave before the check was
+    shared (recorded from that build), under that entry point's own name"""
+    from pcr_amd import _lib
+    lib = _lib.load()
+    one = 0x1000  # never dereferenced: every call below is refused
+    fn = getattr(lib, entry)
+    rng, null = ICP_ENTRY_NAMES[entry]
+
+    def call(p=1, n1=16, n2=16, dist=0.2, iters=10, rf=1e-6, rr=1e-6, transform=one):
+        head = (one, one) + ((one,) if entry.endswith("plane") else ()) + (p, n1, n2)
+        counts = () if entry == "pcr_icp_point_to_point" else (None, None)
+        return fn(*head, *counts, None, dist, iters, rf, rr, transform, one, one, one, one, one,
+                  one, None)
+    for kw, text in ICP_ERRORS:
+        assert call(**kw) == -1, (entry, kw)
+        assert lib.pcr_last_error() == text.format(range=rng, null=null).encode(), (entry, kw)
+
+
 def test_cpu_tensors_rejected():
     import torch
     from pcr_amd import ops
